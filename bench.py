@@ -7,10 +7,14 @@ A step = one word-count job over device-resident synthetic input: reset tables -
   N > 1: BASELINE config 3 (16 GiB of the same generator, seed 43, nReduce 64) split over the
          N ranks (strong scaling): map -> export by owner (ihash % 64) % N -> RCCL all-to-all-v ->
          owners import, sort and format their partitions -> rank 0 merges the owners' sorted runs.
-After the timed steps the merged file is checked byte for byte against the C oracle (N > 1:
-against the sum of every rank's oracle counts); a mismatch exits 3 without printing a rate.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, runs W warm-up and K timed steps of the loop its value is made of, writes the
+last job's merged file with --dump-outputs, and prints one JSON line.  --full adds everything else:
+after the timed steps the merged file is checked byte for byte against the C oracle (N > 1:
+against the sum of every rank's oracle counts; a mismatch exits 3 without printing a rate), N = 1
+also times the one-engine loops, and the line carries per-phase times, the end-to-end file job
+and the CPU baselines.
 N > 1: one rank per GPU (backend nccl = RCCL).  Started by an external torch.distributed.run, or,
 when WORLD_SIZE is not set, by this script itself (wcg/launch.py) before any GPU call.
 """
@@ -44,6 +48,13 @@ def parse():
                          "c3_ascii_zipf_16gib at N > 1 (BASELINE config 3: 16 GiB strong-scaled over N, nReduce 64)")
     ap.add_argument("--bytes", type=int, default=None, help="total input bytes (default: the workload's size)")
     ap.add_argument("--nreduce", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline loop: the check of the result against the oracle, the other "
+                         "step loops (N = 1), the instrumented phase steps, the end-to-end file job and the "
+                         "CPU baselines (the --no-* switches below leave single legs out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed job left (the merged file) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--cpu-sample-mib", type=int, default=256)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true")
@@ -63,6 +74,25 @@ def parse():
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="PMC-derived HBM bytes per map launch (written by tools/pmc_traffic.py)")
     return ap.parse_args()
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, merged):
+    """--dump-outputs: what a caller of the timed path receives from its last job, the merged
+    "key: count\\n" file (wcg_result_copy), as merged.npy (one float32 per byte; of a file too large
+    for the 64 MB cap, the bytes at a fixed seeded set of offsets), and merged_size.npy (float64:
+    the file's bytes and lines, a line per key)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    b = np.frombuffer(merged, dtype=np.uint8)
+    cap = (DUMP_CAP_BYTES - 4096) // 4
+    if b.size > cap:
+        b = b[np.unique(np.random.default_rng(0).integers(0, b.size, cap))]
+    np.save(os.path.join(directory, "merged.npy"), b.astype(np.float32))
+    np.save(os.path.join(directory, "merged_size.npy"),
+            np.array([len(merged), merged.count(b"\n")], dtype=np.float64))
 
 
 def _timed_file_port(fn, data, fname):
@@ -389,36 +419,47 @@ def main():
                 engs[j].reduce_wait()
                 pend[j] = False
 
-    for _ in range(args.warmup):
-        step(pipe)
-    if pipe:
-        eng.reduce_wait()
-    eng.enable_timing(3)                      # a new epoch: the timed steps only
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    # N > 1 (and --sync-steps): every step ends in a host wait (wcg_reduce reads back the formatted
-    # size; the N > 1 Merge is synchronous at root), so the host clock between steps times each step
-    t0 = time.perf_counter()
-    marks = [t0]
-    for _ in range(args.steps):
-        step(pipe)
-        marks.append(time.perf_counter())
-    if pipe:
-        eng.reduce_wait()                     # the last job's sizes and status (errors surface here)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    dt = time.perf_counter() - t0
-    step_ms = [(b - a) * 1e3 for a, b in zip(marks, marks[1:])]
-    if world > 1:
-        tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if gloo else "cuda")
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
-    map_sum, map_launches = eng.timings()         # k_map device ms, summed over the timed steps
-    assert map_launches == args.steps, (map_launches, args.steps)
-    synced_ms = None
-    if pipe:
+    # A plain run times one K-step loop, the one its value is made of: at N = 1 the multi-context
+    # loop (with --contexts 1 the one-engine pipelined loop, with --sync-steps the synced one), at
+    # N > 1 the ranks' loop.  --full also runs the other N = 1 loops (the fastest is then the
+    # value, step_mode names it), the instrumented phase steps, the check against the oracle, the
+    # end-to-end file job and the CPU baselines.
+    full = args.full
+    one_engine_loop = full or not two
+    dt = map_sum = synced_ms = two_ms = None
+    step_ms = []
+    last = eng                                # the engine that ran the last timed job
+    if one_engine_loop:
+        for _ in range(args.warmup):
+            step(pipe)
+        if pipe:
+            eng.reduce_wait()
+        eng.enable_timing(3)                      # a new epoch: the timed steps only
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        # N > 1 (and --sync-steps): every step ends in a host wait (wcg_reduce reads back the formatted
+        # size; the N > 1 Merge is synchronous at root), so the host clock between steps times each step
+        t0 = time.perf_counter()
+        marks = [t0]
+        for _ in range(args.steps):
+            step(pipe)
+            marks.append(time.perf_counter())
+        if pipe:
+            eng.reduce_wait()                     # the last job's sizes and status (errors surface here)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        dt = time.perf_counter() - t0
+        if not pipe:
+            step_ms = [(b - a) * 1e3 for a, b in zip(marks, marks[1:])]
+        if world > 1:
+            tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if gloo else "cuda")
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            dt = float(tt.item())
+        map_sum, map_launches = eng.timings()         # k_map device ms, summed over the timed steps
+        assert map_launches == args.steps, (map_launches, args.steps)
+    if pipe and full:
         # the same K jobs with a host wait at the end of each (wcg_reduce): the per-step spread on
         # the host clock, and the rate a caller that waits for every job sees
         torch.cuda.synchronize()
@@ -430,9 +471,9 @@ def main():
         torch.cuda.synchronize()
         synced_ms = (time.perf_counter() - ts) / args.steps * 1e3
         step_ms = [(b - a) * 1e3 for a, b in zip(marks, marks[1:])]
-    two_ms = None
     if two:
-        # the third loop (after W warm-up jobs of its own): K jobs alternating between the engines
+        # the multi-context loop (after W warm-up jobs of its own): K jobs alternating between the
+        # engines.  A plain run's only loop; with --full the third
         eng.enable_timing(0)
         for i in range(args.warmup):
             step2(i)
@@ -444,12 +485,15 @@ def main():
         drain2()                                  # every job's read-back (errors surface here)
         torch.cuda.synchronize()
         two_ms = (time.perf_counter() - t2) / args.steps * 1e3
+        last = engs[(args.steps - 1) % len(engs)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last.result())
     stats = eng.stats()
-    # every phase (events around each), on instrumented steps after the timed region; N > 1 also
+    # --full: every phase (events around each), on instrumented steps after the timed region; N > 1 also
     # times the step's stages on the host clock with a synchronise after each (the shuffle through
     # gloo, host-staged, has no engine events; RCCL's wcg_exchange / wcg_gather_merge have them)
-    psteps = max(1, min(args.steps, 10))
-    eng.enable_timing(2)
+    psteps = max(1, min(args.steps, 10)) if full else 0
+    eng.enable_timing(2 if full else 0)
     wall = {"map": 0.0, "shuffle": 0.0, "owner_reduce": 0.0, "gather_merge": 0.0}
     map_stats = None
     for _ in range(psteps):
@@ -476,18 +520,20 @@ def main():
         for k, a, b in (("map", t0p, t1p), ("shuffle", t1p, t2p), ("owner_reduce", t2p, t3p),
                         ("gather_merge", t3p, t4p)):
             wall[k] += (b - a) * 1e3
-    ph_sum, _ = eng.timings()
+    ph_sum = eng.timings()[0] if full else {}
     eng.enable_timing(0)
-    if world > 1:                                 # every rank's counters and phase times
+    if world > 1:                                 # every rank's counters and (--full) phase times
         per_rank = [None] * world
-        dist.all_gather_object(per_rank, {"stats": stats, "step_ms": step_ms, "phase_ms_avg":
-                                          {k: round(v / psteps, 4) for k, v in ph_sum.items()},
-                                          "phase_wall_ms_avg": {k: round(v / psteps, 4) for k, v in wall.items()},
-                                          "map_stats": map_stats})
+        mine = {"stats": stats, "step_ms": step_ms}
+        if full:
+            mine.update({"phase_ms_avg": {k: round(v / psteps, 4) for k, v in ph_sum.items()},
+                         "phase_wall_ms_avg": {k: round(v / psteps, 4) for k, v in wall.items()},
+                         "map_stats": map_stats})
+        dist.all_gather_object(per_rank, mine)
 
-    # ---- verify the last step's output against the oracle (outside the timed region)
+    # ---- --full: verify the last step's output against the oracle (outside the timed region)
     verified = None
-    if not args.no_verify:
+    if full and not args.no_verify:
         from tests import oracle_bridge as ob
         data = host.numpy().tobytes()
         if world == 1:
@@ -516,22 +562,26 @@ def main():
             sys.exit(3)
 
     if rank == 0:
-        ms_step = dt / args.steps * 1e3
-        # N = 1: two or three K-step loops ran the same full jobs (contexts: jobs dealt in turn to
-        # --contexts engines on their own streams; pipelined: reset, map, wcg_reduce_async back to back
-        # on one engine; synced: every job waits for its reduce's read-back), each bracketed by
-        # torch.cuda.synchronize(); the fastest is the value and step_mode names it (on the
-        # round-5 driver box the synced loop was the faster of the one-engine loops by 0.9 %, on
-        # the builder's box the pipelined one by 1.7 %: box-to-box variance)
-        mode_used = "pipelined" if pipe else "synced"
+        # N = 1 with --full: two or three K-step loops ran the same full jobs (contexts: jobs dealt in
+        # turn to --contexts engines on their own streams; pipelined: reset, map, wcg_reduce_async back
+        # to back on one engine; synced: every job waits for its reduce's read-back), each bracketed
+        # by torch.cuda.synchronize(); the fastest is the value and step_mode names it (between two
+        # boxes the synced loop was the faster of the one-engine loops by 0.9 % on one, the
+        # pipelined one by 1.7 % on the other).  A plain run has one loop, and it is the value.
+        if dt is None:
+            ms_step, mode_used = two_ms, "contexts"
+        else:
+            ms_step, mode_used = dt / args.steps * 1e3, "pipelined" if pipe else "synced"
         ms_pipelined = ms_step if pipe else None
         if synced_ms is not None and synced_ms < ms_step:
-            ms_step, dt, mode_used = synced_ms, synced_ms * args.steps / 1e3, "synced"
+            ms_step, mode_used = synced_ms, "synced"
         if two_ms is not None and two_ms < ms_step:
-            ms_step, dt, mode_used = two_ms, two_ms * args.steps / 1e3, "contexts"
+            ms_step, mode_used = two_ms, "contexts"
+        dt = ms_step * args.steps / 1e3
         all_bytes = total if strong else n * world
         gbs = all_bytes / (dt / args.steps) / 1e9
-        avg_map_ms = map_sum["map"] / args.steps      # HIP events over the timed steps
+        # HIP events over the one-engine loop's timed steps (a plain multi-context run has none)
+        avg_map_ms = map_sum["map"] / args.steps if map_sum is not None else 0.0
         achieved = n / (avg_map_ms * 1e-3) / 1e9 if avg_map_ms > 0 else None
         traffic = None
         try:
@@ -573,7 +623,11 @@ def main():
                                         "kernels share the CUs)" if pipe else
                                         "HIP events around every k_map launch of the timed loop"},
         }
-        # per-step spread (host clock between steps; N > 1: each step's slowest rank)
+        out["full"] = full
+        if map_sum is None:                       # a plain multi-context run: no events around k_map
+            del out["roofline"]
+        # per-step spread (host clock between steps; N > 1: each step's slowest rank); N = 1 with
+        # pipelined jobs: from the synced loop of --full
         if world > 1:
             srt = sorted(max(v) for v in zip(*[r["step_ms"] for r in per_rank]))
         else:
@@ -581,26 +635,29 @@ def main():
 
         def q(f):
             return round(srt[min(len(srt) - 1, int(f * (len(srt) - 1) + 0.5))], 4)
-        out["ms_per_step_median"] = q(0.5)
-        out["ms_per_step_spread"] = {"min": q(0.0), "p10": q(0.1), "p90": q(0.9), "max": q(1.0),
-                                     "how": ("host clock between the steps of a second K-step loop in which "
-                                             "every step waits for its reduce (wcg_reduce); value uses the "
-                                             "mean over the fastest of the bracketed loops (step_mode)" if pipe else
-                                             "host clock between steps (each step ends in a host wait); "
-                                             "value uses the mean over the bracketed loop")}
+        if srt:
+            out["ms_per_step_median"] = q(0.5)
+            out["ms_per_step_spread"] = {"min": q(0.0), "p10": q(0.1), "p90": q(0.9), "max": q(1.0),
+                                         "how": ("host clock between the steps of a second K-step loop in which "
+                                                 "every step waits for its reduce (wcg_reduce); value uses the "
+                                                 "mean over the fastest of the bracketed loops (step_mode)" if pipe else
+                                                 "host clock between steps (each step ends in a host wait); "
+                                                 "value uses the mean over the bracketed loop")}
+            out["value_at_median_step"] = round(all_bytes / (q(0.5) * 1e-3) / 1e9, 3)
         out["step_mode"] = {
             "contexts": f"{nctx} contexts: jobs dealt in turn to {nctx} engines, each on its own stream and "
                         "hardware queue (reset, map, wcg_reduce_async; an engine's previous job is waited for "
                         "before its reuse), so one job's map runs on the CUs another's aggregation tail and "
-                        "reduce leave idle; every job runs in full, every engine's last output verified; the "
-                        "last jobs' read-backs waited for inside the timed region",
+                        "reduce leave idle; every job runs in full, every engine's last output verified "
+                        "(--full); the last jobs' read-backs waited for inside the timed region",
             "pipelined": "pipelined: reset, map, wcg_reduce_async per job, back to back on one stream; the last "
                          "job's read-back waited for inside the timed region",
             "synced": "synchronous: each job ends in its reduce's host read-back (wcg_reduce)"}[mode_used]
         if two_ms is not None:
             out["loop_order"] = ("after W warm-up jobs: the pipelined loop (the first, so it carries the GPU's "
                                  "clock ramp from idle), the synced loop, then W more warm-up jobs and the "
-                                 "multi-context loop")
+                                 "multi-context loop" if full else
+                                 "W warm-up jobs, then the K timed jobs, all in the multi-context loop")
             out["contexts"] = nctx
             out["ms_per_step_contexts"] = round(two_ms, 4)
             out["value_contexts"] = round(all_bytes / (two_ms * 1e-3) / 1e9, 3)
@@ -609,12 +666,12 @@ def main():
             out["value_pipelined"] = round(all_bytes / (ms_pipelined * 1e-3) / 1e9, 3)
             out["ms_per_step_host_synced"] = round(synced_ms, 4)
             out["value_host_synced"] = round(all_bytes / (synced_ms * 1e-3) / 1e9, 3)
-        out["value_at_median_step"] = round(all_bytes / (q(0.5) * 1e-3) / 1e9, 3)
         out["stats"] = stats
-        out["phase_ms_avg"] = {k: round(v / psteps, 4) for k, v in ph_sum.items()
-                               if world > 1 or k in ("map", "agg", "compact", "sort", "format")}
-        out["phase_timing"] = (f"HIP events around every phase on {psteps} instrumented steps after the "
-                               "timed region (the timed steps carry events around k_map only)")
+        if full:
+            out["phase_ms_avg"] = {k: round(v / psteps, 4) for k, v in ph_sum.items()
+                                   if world > 1 or k in ("map", "agg", "compact", "sort", "format")}
+            out["phase_timing"] = (f"HIP events around every phase on {psteps} instrumented steps after the "
+                                   "timed region (the timed steps carry events around k_map only)")
         if world == 1:
             fused = eng.reduce_path() == 1
             out["reduce_path"] = ("one launch (csrc/wcg_fused.h): compaction, sort and formatting in one "
@@ -626,14 +683,15 @@ def main():
             # exchange (RCCL send/recv of the units), import, gather (RCCL runs -> rank 0),
             # merge (k-way merge of the runs at rank 0)
             out["per_rank"] = per_rank
+        if world > 1 and full:
             out["phase_ms_avg_max_over_ranks"] = {
                 k: max(r["phase_ms_avg"][k] for r in per_rank) for k in per_rank[0]["phase_ms_avg"]}
             out["phase_wall_ms_avg_max_over_ranks"] = {
                 k: max(r["phase_wall_ms_avg"][k] for r in per_rank) for k in per_rank[0]["phase_wall_ms_avg"]}
         out["verified_vs_oracle"] = verified
-        if world == 1 and not args.no_end_to_end:
+        if full and world == 1 and not args.no_end_to_end:
             out["end_to_end"] = end_to_end(keys_cap, cfg, n)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], out["cpu_baseline_parallel"], out["cpu_restatement_all_cores"] = \
                 cpu_baselines(cfg, args.cpu_sample_mib << 20)
         print(json.dumps(out), flush=True)

@@ -21,6 +21,7 @@ import time
 import pytest
 
 from tests.oracle_bridge import wc_ref
+from tests.test_mr_workers import sock  # noqa: F401  (fixture: a short directory for the sockets)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "mit-6.824-2015_amd")
@@ -44,15 +45,13 @@ class Proc:
                 self.dojob.set()
 
 
-def _run(tmp_path, worker_argv, nmap=32, nreduce=64, nbytes=24 << 20, kill_one=True, timeout=300):
+def _run(tmp_path, sock, worker_argv, nmap=32, nreduce=64, nbytes=24 << 20, kill_one=True, timeout=300):
     from wcg import mr
     from wcg.corpus import Generator, CONFIGS
     cfg = CONFIGS["c2_ascii_zipf_1gib"]
     data = Generator(cfg["mode"], cfg["vocab"], cfg["zipf_s"], cfg["seed"]).bytes(nbytes)
     path = tmp_path / "824-mrinput.txt"
     path.write_bytes(data)
-    sock = tmp_path / "sock"
-    sock.mkdir()
     master = str(sock / "mr-master")
     job = mr.MapReduce(nmap, nreduce, str(path), master, str(tmp_path))
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([PKG, ROOT]), PYTHONUNBUFFERED="1")
@@ -96,11 +95,11 @@ def _standin_argv(tmp):
                                      str(nrpc), str(tmp)]
 
 
-def test_worker_processes_sigkill_cpu_standin(tmp_path):
-    _run(tmp_path, _standin_argv(tmp_path), nbytes=3 << 20)
+def test_worker_processes_sigkill_cpu_standin(tmp_path, sock):
+    _run(tmp_path, sock, _standin_argv(tmp_path), nbytes=3 << 20)
 
 
 @pytest.mark.gpu
-def test_worker_processes_sigkill_gpu(tmp_path, built):
+def test_worker_processes_sigkill_gpu(tmp_path, sock, built):
     # wc.go's worker CLI (nRPC = 100; the budget knob WCG_NRPC is set per process by _run)
-    _run(tmp_path, lambda master, me, nrpc: [sys.executable, "-m", "wcg.wc", "worker", master, me])
+    _run(tmp_path, sock, lambda master, me, nrpc: [sys.executable, "-m", "wcg.wc", "worker", master, me])

@@ -9,6 +9,9 @@ HIP engine. Every test checks:
   * that CleanupFiles finds exactly the reference's file names.
 """
 import os
+import pathlib
+import shutil
+import tempfile
 import threading
 import time
 
@@ -76,12 +79,22 @@ def _expected(data):
     return wc_ref.word_count(text)
 
 
-def _run(tmp_path, factory, nmap, nreduce, schedule, timeout=240):
+@pytest.fixture
+def sock():
+    """A directory for the RPC sockets.  An AF_UNIX address holds at most 107 bytes, which a
+    tmp_path under a deep home or TMPDIR exceeds; the reference keeps its sockets under
+    /var/tmp/824-<uid>/ and not in the working directory (test_test.go:112-121)."""
+    d = tempfile.mkdtemp(prefix="wcg-", dir="/tmp" if os.access("/tmp", os.W_OK) else None)
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def _run(tmp_path, sock, factory, nmap, nreduce, schedule, timeout=240):
     """schedule(master_addr, start_worker) starts workers (possibly over time)."""
     from wcg import mr
     path, data = _input(tmp_path)
-    sock = tmp_path / "sock"
-    sock.mkdir()
     master = str(sock / "mr-master")
     job = mr.MapReduce(nmap, nreduce, path, master, str(tmp_path))
     workers = []
@@ -127,8 +140,8 @@ def _many_failures(start, stop):
 
 @pytest.mark.parametrize("name,schedule", [("basic", _basic), ("one_failure", _one_failure),
                                            ("many_failures", _many_failures)])
-def test_master_workers_cpu_standin(tmp_path, name, schedule):
-    job, workers = _run(tmp_path, StandInEngine, nmap=20, nreduce=10, schedule=schedule)
+def test_master_workers_cpu_standin(tmp_path, sock, name, schedule):
+    job, workers = _run(tmp_path, sock, StandInEngine, nmap=20, nreduce=10, schedule=schedule)
     if name == "basic":                     # checkWorker: every worker did at least one job
         assert len(job.stats) == 2 and all(n > 0 for n in job.stats), job.stats
         # worker.go:40-43: each worker's Njobs counts its DoJob connections plus the Shutdown RPC's
@@ -184,9 +197,9 @@ def test_json_intermediates_cpu_standin(tmp_path):
 
 
 @pytest.mark.gpu
-def test_master_workers_gpu(tmp_path, built):
+def test_master_workers_gpu(tmp_path, sock, built):
     import wcg
-    _run(tmp_path, lambda: wcg.Engine(0, 1 << 20, 1 << 18), nmap=8, nreduce=5, schedule=_one_failure)
+    _run(tmp_path, sock, lambda: wcg.Engine(0, 1 << 20, 1 << 18), nmap=8, nreduce=5, schedule=_one_failure)
 
 
 @pytest.mark.gpu

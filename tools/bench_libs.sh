@@ -6,7 +6,7 @@ if [ "$1" == "--args" ]; then ARGS=$2; shift 2; fi
 mkdir -p "$OUT"
 for L in "$@"; do
   tag=$(basename "${L:-default}" .so)
-  WCG_LIB=$L timeout -k 10 180 python3 bench.py $ARGS > "$OUT/$tag.json" 2> "$OUT/$tag.err" || exit $?
+  WCG_LIB=$L timeout -k 10 180 python3 bench.py --full $ARGS > "$OUT/$tag.json" 2> "$OUT/$tag.err" || exit $?
   python3 -c "
 import json,sys
 d=json.loads(open('$OUT/$tag.json').read().strip().splitlines()[-1])

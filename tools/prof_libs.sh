@@ -6,6 +6,6 @@ mkdir -p "$OUT"
 for L in "$@"; do
   tag=$(basename "$L" .so)
   WCG_LIB=$L timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$tag" -o run -- \
-    python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-verify --no-end-to-end \
+    python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-verify --no-end-to-end \
     --workload c4_utf8_zipf_64gib --bytes 1073741824 > "$OUT/$tag.log" 2>&1 || exit $?
 done
