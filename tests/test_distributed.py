@@ -8,7 +8,6 @@ runs on rank 0 against the oracle.
 """
 import os
 import socket
-import struct
 
 import pytest
 import torch
@@ -16,40 +15,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from tests.oracle_bridge import wc_ref
-
-LONG_FLAG = 1 << 63
-CONT_MARK = 1 << 62
-
-
-def encode(key: bytes, cnt: int) -> bytes:
-    """libwcg record units (csrc/wcg_reduce.h: k_export_write)."""
-    if len(key) <= 15:
-        pad = key + b"\0" * (16 - len(key))
-        hi, lo = struct.unpack(">QQ", pad)
-        return struct.pack("<QQQQ", hi, lo, cnt, len(key))
-    hi, lo = struct.unpack(">QQ", key[:16])
-    out = struct.pack("<QQQQ", hi, lo, cnt, LONG_FLAG | (len(key) << 40))
-    for i in range(0, len(key), 24):
-        chunk = key[i:i + 24].ljust(24, b"\0")
-        out += chunk + struct.pack("<Q", CONT_MARK)
-    return out
-
-
-def decode(buf: bytes):
-    i, n = 0, len(buf) // 32
-    while i < n:
-        hi, lo, cnt, ref = struct.unpack_from("<QQQQ", buf, 32 * i)
-        assert ref != CONT_MARK, "continuation unit without header"
-        if ref & LONG_FLAG:
-            ln = (ref >> 40) & ((1 << 23) - 1)
-            nu = (ln + 23) // 24
-            raw = b"".join(buf[32 * (i + 1 + k): 32 * (i + 1 + k) + 24] for k in range(nu))
-            yield raw[:ln], cnt
-            i += 1 + nu
-        else:
-            key = struct.pack(">QQ", hi, lo)[:ref]
-            yield key, cnt
-            i += 1
+from tests.wire import CONT_MARK, LONG_FLAG, decode, encode  # noqa: F401
 
 
 class OracleEngine:
