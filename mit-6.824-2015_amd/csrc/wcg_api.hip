@@ -271,6 +271,29 @@ int ensure_recs(wcg_ctx* c, u64 n) {
     return WCG_OK;
 }
 
+// tests: a capacity override (tests/test_gpu_capacity.py), read on every call like WCG_FUSED_TARGET
+// so that one process can set and unset it.  WCG_REGION_CAP, WCG_RP_CAP2, WCG_LONG_PART_CAP and
+// WCG_EMIT_CAP shrink a capacity the kernels already receive as an argument, so that a few MiB of
+// text fill the buffer and take its "full" branch; no kernel knows of them.  The buffers are sized
+// after the override and only ever grow, so any accepted value is backed by memory.
+// A value must hold for all calls of one job (set before the first map call, unset after the reduce).
+bool cap_env(const char* name, u64* v) {
+    const char* e = getenv(name);
+    if (!e) return false;
+    *v = strtoull(e, nullptr, 10);
+    return true;
+}
+
+// the length of the pass-2 record log (the map kernels stop appending there, compaction reads
+// min(nemit, this)).  WCG_EMIT_CAP (tests) may only lower it: the log stays dense only if every
+// call of a job and its compaction use one length.  The allocation keeps the full size.
+u64 emit_log_alloc(const wcg_ctx* c) { return c->max_keys + 65536; }
+u64 emit_log_cap(const wcg_ctx* c) {
+    u64 cap = emit_log_alloc(c), v;
+    if (cap_env("WCG_EMIT_CAP", &v)) cap = std::min(cap, v);
+    return cap;
+}
+
 // tables -> compacted records (c->crec).  Two-pass jobs append the tables' records to the
 // record log itself (no copy of the log); otherwise, or when the log's buffer cannot hold them,
 // the log is copied to the front of recA and the tables follow.  The record buffers start at
@@ -322,7 +345,7 @@ int compact(wcg_ctx* c, bool defer = false) {
     if (!scan_gtab) gs = 0;
     c->counts_clean = false;
     const u64 total = gs + ls;
-    const u64 emit_cap = c->max_keys + 65536;     // the log's length: min(nemit, emit_cap)
+    const u64 emit_cap = emit_log_cap(c);         // the log's length: min(nemit, emit_cap)
     if (c->two_pass_used && c->remit) {
         HIPCHK(c, hipMemsetAsync(&c->st->nlong, 0, sizeof(u64), c->stream));
         if (c->timing_all) { c->phase_ev[0] = take_event(c); HIPCHK(c, hipEventRecord(c->phase_ev[0], c->stream)); }
@@ -1380,6 +1403,15 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
     static const char* rpad_env = getenv("WCG_REGION_PAD");   // measurement: units added to a region
     if (rpad_env && a.region_cap + (u64)(atoi(rpad_env) & ~1) <= (1ull << 31) / (8ull * P))
         a.region_cap += (u64)(atoi(rpad_env) & ~1);
+    // tests: units per region (cap_env above).  Any even value from 4 up is safe: an even length
+    // keeps every region 16-byte aligned for k_agg's and k_rp's v4u loads; their unmasked reads run at
+    // most 258 units past a region's start, inside the pool's AGG_SLACK_UNITS whatever the length;
+    // units at or past region_len are masked to fillers, and k_map zeroes a cut-off entry's units.
+    // 4 and not 2, so that the largest entry (a flushed medium key with a count: 3 units) fits an
+    // empty region.
+    u64 rcap_env;
+    if (cap_env("WCG_REGION_CAP", &rcap_env))
+        a.region_cap = std::min<u64>(std::max<u64>(4, rcap_env), (1ull << 31) / (8ull * P)) & ~1ull;
     a.pmask = P - 1;
     u64 need = (grid * P * a.region_cap + AGG_SLACK_UNITS) * sizeof(u64);
     if (need > c->pool_bytes) {
@@ -1430,8 +1462,8 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
     // to the global table.  Two-pass jobs keep the global table empty: pass 2's records, its
     // overflow and k_long_hash's inline runs all go to the record log.
     const bool two_pass = two_pass0;
-    const u64 rec_cap_emit = c->max_keys + 65536;
-    RC(ensure(c, &c->remit, &c->remit_cap, rec_cap_emit));
+    const u64 rec_cap_emit = emit_log_cap(c);
+    RC(ensure(c, &c->remit, &c->remit_cap, emit_log_alloc(c)));
     a.emit = two_pass ? c->remit : nullptr;
     a.emit_cap = rec_cap_emit;
     a.pool = c->pool;
@@ -1504,6 +1536,8 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
         LongPart lp;
         const u64 expect = grid * (u64)a.tiles_per_wg * 16;     // 16 per step: 3x C4's rate
         lp.cap = (u32)std::min<u64>(std::max<u64>(1024, (expect * 5 / 4 + LQ - 1) / LQ), 0x7FFFFFFFull);
+        u64 lcap_env;                   // tests: entries per partition, >= 1 (cap_env above)
+        if (cap_env("WCG_LONG_PART_CAP", &lcap_env)) lp.cap = (u32)std::min<u64>(std::max<u64>(1, lcap_env), 0x7FFFFFFFull);
         RC(ensure(c, &c->lent, &c->lent_cap, (u64)LQ * lp.cap));
         u32* const old_cur = c->lpcur;
         RC(ensure(c, &c->lpcur, &c->lpcur_cap, (u64)LQ));
@@ -1582,7 +1616,11 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
     const u32 sl = std::max<u32>(1, std::min<u32>((u32)grid, rps_env ? (u32)atoi(rps_env) : 2 * g.slices));
     const u32 nrp = P * sl;
     const u64 slice_cap = (u64)cdiv(grid, sl) * a.region_cap;
-    const u64 cap2 = ((slice_cap * 3 / 2) / AGG_Q + 1024) & ~1ull;
+    u64 cap2 = ((slice_cap * 3 / 2) / AGG_Q + 1024) & ~1ull;
+    // tests: units per sub-bucket region, even and >= 2 (cap_env above; pass 2 walks these regions
+    // as pass 1 walks k_map's: see WCG_REGION_CAP)
+    u64 cap2_env;
+    if (cap_env("WCG_RP_CAP2", &cap2_env)) cap2 = std::max<u64>(2, std::min<u64>(cap2_env, 1ull << 31)) & ~1ull;
     RC(ensure(c, &c->pool2, &c->pool2_cap, (u64)nrp * AGG_Q * cap2 + AGG_SLACK_UNITS));
     RC(ensure(c, &c->rlen2, &c->rlen2_cap, (u64)nrp * AGG_Q));
     RpArgs rp;
