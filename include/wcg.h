@@ -142,6 +142,25 @@ WCG_API int wcg_partition(wcg_ctx *ctx, uint32_t nreduce, uint32_t r, uint8_t *h
 WCG_API int wcg_partition_all(wcg_ctx *ctx, uint32_t nreduce, uint8_t *host_out, uint64_t cap,
                               uint64_t *part_bytes);
 
+/* The n most frequent words: the bytes that `LC_ALL=C sort -n -k2 <merged file> | tail -n <n>`
+ * prints for the merged file of the last wcg_reduce() - the reference's acceptance check of word
+ * count (src/main/test-wc.sh:2-3, with n = 10, diffed against mr-testout.txt).  Lines
+ * "key: count\n", ascending by count (compared as unsigned 64-bit), lines of equal count ascending
+ * by bytewise key, the last min(n, keys) of that order; selected and formatted on the device from
+ * the sorted records, so only those lines cross to the host.  *nlines / *nbytes get their number
+ * and size; host_out == NULL queries them only (the lines stay cached on the device for this n
+ * until the next job, so a second call with the same n is a copy).  n == 0: no lines;
+ * n > WCG_TOP_MAX: WCG_EINVAL (take the merged file).  Requires a prior wcg_reduce() (a pending
+ * wcg_reduce_async job is waited for): WCG_ESTATE before one, after wcg_free of its result, and
+ * after wcg_merge_runs / wcg_gather_merge* on the context that holds the merged file (its records
+ * are lines without counts; wcg.top_merge in Python combines the ranks' tops instead).  The result
+ * calls, wcg_partition*, wcg_export*, wcg_stats and wcg_timings in between do not disturb it (they
+ * leave the sorted records alone; should an export ever have to regrow the record buffers,
+ * wcg_top reports WCG_ESTATE rather than read freed records). */
+#define WCG_TOP_MAX 1024
+WCG_API int wcg_top(wcg_ctx *ctx, uint32_t n, uint8_t *host_out, uint64_t cap, uint64_t *nlines,
+                    uint64_t *nbytes);
+
 /* DoMap's reference-exact intermediate files (mapreduce.go:214-230) for one split: for every
  * token, in input order, the line {"Key":"tok","Value":"1"}\n in file ihash(tok) % nreduce - the
  * bytes the reference's json.Encoder writes to mrtmp.<f>-<m>-<r>, so an unmodified CPU DoReduce

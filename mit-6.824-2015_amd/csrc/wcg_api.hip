@@ -29,6 +29,7 @@
 #include "wcg_map.h"
 #include "wcg_agg.h"
 #include "wcg_reduce.h"
+#include "wcg_top.h"
 #include "wcg_fused.h"
 #include "wcg_ingest.h"
 
@@ -98,6 +99,16 @@ struct wcg_ctx {
     u32* pid = nullptr; u64 pid_cap = 0;
     u64* d_partb = nullptr; u64 partb_cap = 0;
     uint8_t* d_part = nullptr; u64 part_cap = 0;
+    // the n highest-count lines (wcg_top): valid for top_n while reduced, cached like the partitions
+    u32 top_n = 0;
+    u64 top_lines = 0, top_bytes = 0;
+    u64* top_cand = nullptr; u64 top_cand_cap = 0;   // k_top_select's survivors (wcg_top.h: TOP_HDR + items)
+    Rec* top_rec = nullptr; u64 top_rec_cap = 0;     // the chosen records, ascending
+    uint8_t* d_top = nullptr; u64 top_cap = 0;       // their lines
+    // c->sorted[0, sorted_n) still holds the last wcg_reduce's records (wcg_top reads them): set by
+    // the reduce; the record buffers' reallocation (a later compaction that needs more) ends it
+    bool sorted_live = false;
+    u64 sorted_n = 0;
     // export
     u32* owner = nullptr; u64 owner_cap = 0;
     u64* d_per_rank = nullptr;                // [2 * 1024]: counts, cursors
@@ -268,6 +279,7 @@ int ensure_recs(wcg_ctx* c, u64 n) {
     HIPCHK(c, hipFree(c->recA));
     HIPCHK(c, hipFree(c->recB));
     c->recA = a; c->recB = b; c->rec_cap = nc;
+    c->sorted_live = false;
     return WCG_OK;
 }
 
@@ -562,6 +574,8 @@ int reduce_fused_finish(wcg_ctx* c) {
     }
     c->nrec_hint = c->nrec;
     c->long_hint = c->h_st->long_tokens;
+    c->sorted_live = true;
+    c->sorted_n = c->nrec;
     return WCG_OK;
 }
 
@@ -1132,7 +1146,8 @@ int wcg_close(wcg_ctx* c) {
                     c->d_part, c->owner, c->d_per_rank, c->exp_buf, c->pool, c->region_len, c->wg_stats,
                     c->llog, c->llog_len, c->smp, c->bid, c->spx, c->irec, c->lent, c->lpcur, c->spill, c->spill_len, c->pool2, c->rlen2, c->remit, c->ovf, c->hist, c->spart, c->ikey, c->iidx, c->groups,
                     c->pid, c->d_partb, c->nlpos, c->d_rb, c->d_b0, c->d_jin, c->d_jout, c->jhist, c->dbig,
-                    c->d_xrow, c->xrecv, c->grecv, c->glist, c->llist, c->fr_buf, c->flist};
+                    c->d_xrow, c->xrecv, c->grecv, c->glist, c->llist, c->fr_buf, c->flist,
+                    c->top_cand, c->top_rec, c->d_top};
     if (c->comm) (void)ncclCommDestroy(c->comm);
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (c->h_x) (void)hipHostFree(c->h_x);
@@ -1267,7 +1282,7 @@ int reset_tables(wcg_ctx* c) {
     c->counts_clean = true;
     c->compacted = c->reduced = c->merged = false;
     c->exp_ready = false;
-    c->part_R = 0;
+    c->part_R = 0; c->top_n = 0;
     c->nrec = 0;
     c->out_len = 0;
     c->two_pass_used = false;
@@ -1655,7 +1670,7 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
     c->map_launches_since_reset++;
     c->compacted = c->reduced = c->merged = false;
     c->exp_ready = false;
-    c->part_R = 0;
+    c->part_R = 0; c->top_n = 0;
     return WCG_OK;
 }
 
@@ -1745,7 +1760,7 @@ int wcg_reduce(wcg_ctx* c, uint64_t* nkeys, uint64_t* nbytes) {
         }
         c->reduced = true;
         c->merged = false;
-        c->part_R = 0;
+        c->part_R = 0; c->top_n = 0;
         if (nkeys) *nkeys = c->nkeys;
         if (nbytes) *nbytes = c->out_len;
         return WCG_OK;
@@ -1788,8 +1803,10 @@ int wcg_reduce(wcg_ctx* c, uint64_t* nkeys, uint64_t* nbytes) {
         else c->nkeys = c->h_scalar[8];
         c->nkeys_on_device = false;
     }
+    c->sorted_live = true;
+    c->sorted_n = c->nrec;
     c->reduced = true;
-    c->part_R = 0;
+    c->part_R = 0; c->top_n = 0;
     if (nkeys) *nkeys = c->nkeys;
     if (nbytes) *nbytes = c->out_len;
     return WCG_OK;
@@ -1813,7 +1830,7 @@ int wcg_reduce_async(wcg_ctx* c) {
     c->pending = true;
     c->reduced = true;
     c->merged = false;
-    c->part_R = 0;
+    c->part_R = 0; c->top_n = 0;
     return WCG_OK;
 }
 
@@ -1939,6 +1956,65 @@ int wcg_partition(wcg_ctx* c, uint32_t nreduce, uint32_t r, uint8_t* host_out, u
     return WCG_OK;
 }
 
+// the last n lines of the merged file in `sort -n -k2` order, in c->d_top (cached until the next job)
+static_assert(TOP_NMAX == WCG_TOP_MAX, "wcg_top.h and wcg.h agree on the largest n");
+static int top_select(wcg_ctx* c, u32 n) {
+    if (n && c->top_n == n) return WCG_OK;
+    const u64 nrec = c->sorted_n;
+    const u32 q = (u32)std::min<u64>(n, nrec);
+    c->top_n = 0;
+    c->top_lines = c->top_bytes = 0;
+    if (q == 0) return WCG_OK;
+    // One workgroup per tile up to TOP_MAXG (4 per CU of 256: all resident, each with two tiles'
+    // loads in flight), and no more than leave the single-workgroup final stage TOP_FINAL survivor
+    // slots (256 tiles): 1024 workgroups up to n = 256, 256 at n = 1024.
+    u64 grid = std::min<u64>(std::min<u64>(cdiv(nrec, TOP_TILE), TOP_MAXG), std::max<u64>(1, TOP_FINAL / n));
+    // tests: WCG_TOP_GRID may only lower the grid (a few thousand keys then give every workgroup
+    // many steps and compactions); read on every call like the capacity knobs above
+    u64 v;
+    if (cap_env("WCG_TOP_GRID", &v)) grid = std::max<u64>(1, std::min(grid, v));
+    RC(ensure(c, &c->top_cand, &c->top_cand_cap, TOP_HDR + 2 * grid * n));
+    RC(ensure(c, &c->top_rec, &c->top_rec_cap, (u64)TOP_NMAX));
+    k_top_select<<<(unsigned)grid, TOP_NT, 0, c->stream>>>(c->sorted, nrec, n, c->top_cand);
+    k_top_final<<<1, TOP_NT, 0, c->stream>>>(c->top_cand, (u32)grid, n, c->sorted, q, c->top_rec);
+    HIPCHK(c, hipGetLastError());
+    // {lines, bytes}: the formatter's buffer is sized exactly (a key may be megabytes long, so a
+    // bound from n alone does not exist, and the merged file's size would double the output memory)
+    u64* const h = c->h_scalar + 16;
+    HIPCHK(c, hipMemcpyAsync(h, c->top_cand + TOP_MAXG, 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const u64 lines = h[0], bytes = h[1];
+    u64 got = 0;
+    RC(format(c, c->top_rec, q, c->arena, FMT_MERGED, 1, 0, bytes, &c->d_top, &c->top_cap, &got));
+    if (got != bytes) { c->err = "wcg_top: formatted size mismatch"; return WCG_EHIP; }
+    c->top_lines = lines;
+    c->top_bytes = bytes;
+    c->top_n = n;
+    return WCG_OK;
+}
+
+int wcg_top(wcg_ctx* c, uint32_t n, uint8_t* host_out, uint64_t cap, uint64_t* nlines, uint64_t* nbytes) {
+    if (!c) return WCG_EINVAL;
+    RC(resolve(c));
+    if (!c->reduced) { c->err = "wcg_top before wcg_reduce"; return WCG_ESTATE; }
+    if (c->merged) { c->err = "wcg_top after wcg_merge_runs (a merged file's records carry no counts)"; return WCG_ESTATE; }
+    if (!c->sorted_live) { c->err = "wcg_top: the sorted records were released (record buffers regrown); wcg_reduce again"; return WCG_ESTATE; }
+    if (n > WCG_TOP_MAX) { c->err = "wcg_top: n above WCG_TOP_MAX (1024)"; return WCG_EINVAL; }
+    int rc = set_dev(c);
+    if (rc) return rc;
+    RC(top_select(c, n));
+    if (nlines) *nlines = c->top_lines;
+    if (nbytes) *nbytes = c->top_bytes;
+    if (host_out) {
+        if (cap < c->top_bytes) { c->err = "wcg_top: buffer too small"; return WCG_EINVAL; }
+        if (c->top_bytes) {
+            HIPCHK(c, hipMemcpyAsync(host_out, c->d_top, c->top_bytes, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    return WCG_OK;
+}
+
 int wcg_export_count(wcg_ctx* c, uint32_t nreduce, uint32_t nranks, uint64_t* counts) {
     if (!c || !counts || nreduce == 0 || nranks == 0 || nranks > EX_MAX_RANKS) return WCG_EINVAL;
     RC(resolve(c));
@@ -2006,7 +2082,7 @@ int wcg_import(wcg_ctx* c, const void* dev_records, uint64_t nrecords) {
     c->imported = true;
     c->compacted = c->reduced = c->merged = false;
     c->exp_ready = false;
-    c->part_R = 0;
+    c->part_R = 0; c->top_n = 0;
     return WCG_OK;          // a full table is reported by the next wcg_reduce / wcg_export_count
 }
 
@@ -2020,7 +2096,7 @@ int wcg_merge_runs(wcg_ctx* c, const void* dev_text, const uint64_t* run_bytes, 
     for (u32 r = 0; r < nruns; r++) total += run_bytes[r];
     c->compacted = false;
     c->exp_ready = false;
-    c->part_R = 0;
+    c->part_R = 0; c->top_n = 0;
     c->reduced = false;
     if (total == 0) {
         c->nrec = 0; c->nkeys = 0; c->out_len = 0; c->reduced = true; c->merged = true;

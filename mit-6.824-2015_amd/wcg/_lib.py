@@ -27,9 +27,10 @@ EXPORTED = [
     "wcg_export_write", "wcg_merge_runs", "wcg_result_copy_device", "wcg_sync", "wcg_free",
     "wcg_comm_id", "wcg_comm_init", "wcg_exchange", "wcg_gather_merge", "wcg_exchange_plan",
     "wcg_gather_plan", "wcg_exchange_local", "wcg_gather_merge_local", "wcg_reduce_path",
-    "wcg_reduce_async", "wcg_reduce_wait", "wcg_ingest_stats",
+    "wcg_reduce_async", "wcg_reduce_wait", "wcg_ingest_stats", "wcg_top",
 ]
 COMM_ID_BYTES = 128
+TOP_MAX = 1024                            # WCG_TOP_MAX
 
 
 class WcgError(RuntimeError):
@@ -89,6 +90,7 @@ def load() -> ctypes.CDLL:
         "wcg_reduce_async": (I, [P]),
         "wcg_reduce_wait": (I, [P, PU64, PU64]),
         "wcg_ingest_stats": (I, [P, ctypes.POINTER(ctypes.c_double), I]),
+        "wcg_top": (I, [P, U32, P, U64, PU64, PU64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -262,6 +264,23 @@ class Engine:
         buf = ctypes.create_string_buffer(max(nb.value, 1))
         self._chk(self._lib.wcg_partition(self._ctx, nreduce, r, buf, nb.value, ctypes.byref(nb)))
         return buf.raw[:nb.value]
+
+    def top_size(self, n: int) -> Tuple[int, int]:
+        """wcg_top with host_out == NULL: (lines, bytes) of top(n); the lines stay on the device."""
+        if not 0 <= n <= 0xFFFFFFFF:
+            raise WcgError(WCG_EINVAL, "top: n out of range")
+        nl, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._lib.wcg_top(self._ctx, n, None, 0, ctypes.byref(nl), ctypes.byref(nb)))
+        return nl.value, nb.value
+
+    def top(self, n: int) -> bytes:
+        """The n most frequent words of the last reduce (n <= TOP_MAX), selected on the device: the
+        bytes `LC_ALL=C sort -n -k2 <merged file> | tail -n <n>` prints (test-wc.sh:2-3)."""
+        _, nb = self.top_size(n)
+        buf = ctypes.create_string_buffer(max(nb, 1))
+        nl2, nb2 = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._lib.wcg_top(self._ctx, n, buf, nb, ctypes.byref(nl2), ctypes.byref(nb2)))
+        return buf.raw[:nb2.value]
 
     def export(self, nreduce: int, nranks: int) -> Tuple[int, List[int]]:
         """Bucket the local aggregate by owner rank; returns (device ptr, units per rank)."""
@@ -442,6 +461,43 @@ def gather_merge_local(engines: List["Engine"], root: int) -> Tuple[int, int]:
         msgs = "; ".join(load().wcg_last_error(e._ctx).decode() for e in engines)
         raise WcgError(st, f"wcg_gather_merge_local: {msgs}")
     return nk.value, nb.value
+
+
+def _count_lines(merged: bytes) -> List[Tuple[int, bytes]]:
+    """(count, key) of every "key: count\\n" line, in the file's order"""
+    out = []
+    for line in merged.split(b"\n"):
+        if line:
+            key, _, cnt = line.rpartition(b": ")
+            out.append((int(cnt), key))
+    return out
+
+
+def _lines_of(items: List[Tuple[int, bytes]]) -> bytes:
+    return b"".join(k + b": " + str(c).encode() + b"\n" for c, k in items)
+
+
+def top_of_merged(merged: bytes, n: int) -> bytes:
+    """What Engine.top(n) computes, stated on the host: the last n lines of the merged file
+    ("key: count\\n" in bytewise key order) after a stable sort by count - the bytes of
+    `LC_ALL=C sort -n -k2 <merged file> | tail -n <n>` (test-wc.sh:2-3).  Counts are Python
+    integers (no width limit); lines of equal count stay in key order."""
+    if n <= 0:
+        return b""
+    items = _count_lines(merged)
+    items.sort(key=lambda it: it[0])                # stable: ties keep the file's key order
+    return _lines_of(items[-n:])
+
+
+def top_merge(parts: List[bytes], n: int) -> bytes:
+    """The global top n from the tops of ranks that own disjoint keys (Engine.top(n) on every rank
+    after exchange + reduce): at most len(parts) * n lines are parsed, no GPU.  The parts are not
+    in one key order, so the order is (count, key bytes) outright."""
+    if n <= 0:
+        return b""
+    items = [it for p in parts for it in _count_lines(p)]
+    items.sort()
+    return _lines_of(items[-n:])
 
 
 def version() -> str:

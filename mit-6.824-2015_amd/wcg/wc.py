@@ -3,6 +3,9 @@
   python -m wcg.wc master <file> sequential          RunSingle(5, 3, ...) on the GPU
   python -m wcg.wc master <file> <master-socket>     MakeMapReduce(5, 3, ...), waits for workers
   python -m wcg.wc worker <master-socket> <me>       RunWorker(..., nRPC = 100) on the GPU
+  python -m wcg.wc top <file> <N>                    the N most frequent words to stdout: what
+                                                     `sort -n -k2 mrtmp.<file> | tail -<N>` prints
+                                                     (test-wc.sh:2-3), selected on the GPU
 
 nMap = 5, nReduce = 3 and nRPC = 100 are wc.go's constants (wc.go:49,51,56).  Environment knobs a
 harness may set without changing that interface: WCG_DEVICE (HIP device of this process, default
@@ -84,6 +87,24 @@ def run_single(path: str, nmap: int = NMAP, nreduce: int = NREDUCE) -> bytes:
     raise AssertionError("unreachable")
 
 
+def top(path: str, n: int = 10) -> bytes:
+    """The n most frequent words of a file (test-wc.sh:2-3: `sort -n -k2 | tail -n`), selected on
+    the GPU: Split + DoMap of the file (map_file, quirk P1 included), reduce, Engine.top.  Tables
+    sized from the input as in run_single; writes no mrtmp.* files."""
+    from ._lib import WcgError, WCG_EFULL
+    size = os.path.getsize(path)
+    for dense in (False, True):
+        with engine_for(size, dense) as e:
+            try:
+                e.map_file(path)
+                e.reduce()
+                return e.top(n)
+            except WcgError as err:
+                if err.status != WCG_EFULL or dense:
+                    raise
+    raise AssertionError("unreachable")
+
+
 def main(argv) -> int:
     if len(argv) != 4:                    # wc.go:45-46: a note, exit status 0
         print(f"{argv[0]}: see usage comments in file")
@@ -94,6 +115,9 @@ def main(argv) -> int:
             run_single(argv[2])
         else:
             mr.MapReduce(NMAP, NREDUCE, argv[2], argv[3], workdir).wait()
+    elif argv[1] == "top":
+        sys.stdout.buffer.write(top(argv[2], int(argv[3])))
+        sys.stdout.buffer.flush()
     else:
         nrpc = int(os.environ.get("WCG_NRPC", str(NRPC)))
         w = mr.Worker(argv[2], argv[3], SizedEngine, os.getcwd(), nrpc,
