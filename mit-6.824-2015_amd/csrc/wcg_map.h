@@ -18,7 +18,7 @@
 //      bytes, fact F4) from aligned dword LDS reads -> the workgroup's LDS tables (exact keys,
 //      u32 counts: MapTable); a miss is appended to this workgroup's region of the miss log for
 //      k_agg; a token > 15 bytes is logged for k_long_hash / long_small.  A list's partial last
-//      iteration is carried in registers into the next step's first iteration (r06);
+//      iteration is carried in registers, undecoded, into the next step's first iteration (r06);
 //   5. after its last step the wave runs its carried tokens, and the workgroup flushes its LDS
 //      table into the miss log too.
 // Token ownership: a token belongs to the 16-byte chunk holding its first byte (exactly once);
@@ -931,9 +931,11 @@ __device__ __forceinline__ u32 wave_incl_scan(u32 x) {
 
 // ABL (measurement builds only, selected by WCG_MAP_ABLATE; results are wrong when ABL != 0):
 //   5 = input loads only, 4 = + LDS staging and letter masks, 1 = + token starts and compaction,
-//   2 = + the per-step decode of both lists' first tokens, 3 = + the short-key iterations' probes
-//   and decodes (no table update, no miss; medium iterations in full); 6 = full but long
-//   tokens only counted, 7 = full but long tokens only measured and hashed
+//   2 = + the per-step reads of both lists' first entries and key words and their merge into the
+//   carried lanes (no decode: a batch is decoded by the iteration that probes it), 3 = + the
+//   short-key iterations' decodes and probes (no table update, no miss, no unit store - and none
+//   counted in the step's stores; medium iterations in full); 6 = full but long tokens only
+//   counted, 7 = full but long tokens only measured and hashed
 // ---- r04: the letter mask of a wave's window with non-ASCII bytes, by a wave-wide list of the
 //      UTF-8 leads.  The lead-compacted form (utf8_mask_lds) decodes eight lead slots per lane,
 //      so a wave pays max-over-lanes (8 on C4: ~615 VALU per step, half of k_map's time there);
@@ -1187,7 +1189,7 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
     //      away; unaligned 8-byte LDS reads cost ~20x the LDS cycles), then the key identity of
     //      fact F4 with byte masks, and its LDS hash
     struct TokS { u64 k; u32 h; };                   // short key (<= 7 bytes): k0 alone
-    struct TokM { u64 k0, k1; u32 h; bool valid; };  // medium key (8-15 bytes); long tokens: !valid
+    struct TokM { u64 k0, k1; u32 h; bool valid; };  // medium key (8-15 bytes); anything else: !valid
     // short key: its bytes lie in [rp & ~3, +12)
     auto keyread_s = [&](u32 e) -> uint3 {
         const u32* q = reinterpret_cast<const u32*>(bytes + ((e & ((1u << SST_LEN_SHIFT) - 1)) & ~3u));
@@ -1208,10 +1210,19 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         const u32* q = reinterpret_cast<const u32*>(bytes + ((e & ((1u << SST_LEN_SHIFT) - 1)) & ~3u));
         return KeyWords{q[0], q[1], q[2], q[3], q[4]};
     };
-    // act: the entry is one of this step's tokens.  A long token (> 15 bytes) is measured and
-    // logged here, while its step's window masks are in LDS (its TokM may be carried to the next
-    // step), and takes no part in the table
-    auto decode_m = [&](u32 e, bool act, const KeyWords& kw, long wbase) -> TokM {
+    // A medium-list entry as it is read (act: it is one of this step's tokens): a long token (> 15
+    // bytes) is measured and logged here, while its step's window masks are in LDS (the entry may
+    // be carried to the next step), and takes no part in the table; a lane past the list's end
+    // keeps entry 0.  Either way the length field is outside 8..15, which is what decode_m tests
+    auto take_m = [&](u32 e, bool act, long wbase) -> u32 {
+        if (act && (e >> SST_LEN_SHIFT) >= 16) {
+            const u32 rp = e & ((1u << SST_LEN_SHIFT) - 1);
+            my_long++;
+            if (ABL != 6) long_token_log<ABL>(a, (u64)(wbase + rp), rp, wmask[wave], &lcur);
+        }
+        return act ? e : 0u;
+    };
+    auto decode_m = [&](u32 e, const KeyWords& kw) -> TokM {
         const u32 rp = e & ((1u << SST_LEN_SHIFT) - 1), len = e >> SST_LEN_SHIFT;
         const u32 bsh = rp & 3u;
         const u32 w0 = __builtin_amdgcn_alignbyte(kw.d1, kw.d0, bsh), w1 = __builtin_amdgcn_alignbyte(kw.d2, kw.d1, bsh);
@@ -1224,22 +1235,24 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         t.k0 = (u64)w1 << 32 | w0;
         t.k1 = (u64)k1h << 32 | k1l;
         t.h = lds_hash32(w0, w1, k1l, k1h);
-        t.valid = act && len < 16;
-        if (act && len >= 16) {
-            my_long++;
-            if (ABL != 6) long_token_log<ABL>(a, (u64)(wbase + rp), rp, wmask[wave], &lcur);
-        }
+        t.valid = nb < 8u;                                 // 8..15 bytes (take_m)
         return t;
     };
 
     // ---- carried tokens (r06).  A list's last, partial iteration is not run in its step: its
-    //      tokens, already decoded, stay in registers (lanes [0, n)) and fill the first lanes of
-    //      the next step's first iteration, whose list reads are shifted by n (entry i of a step's
-    //      list goes to lane (n + i) % 64).  So every iteration but the wave's last two (the drain
-    //      after the main loop) runs 64 tokens, and short keys never take the medium-key body (C2:
-    //      2 short + 1 mixed iteration per step before, ~2.3 short + ~0.3 medium now)
-    TokS cs{0, 0};
-    TokM cm{0, 0, 0, false};
+    //      tokens stay in registers (lanes [0, n)) and fill the first lanes of the next step's
+    //      first iteration, whose list reads are shifted by n (entry i of a step's list goes to
+    //      lane (n + i) % 64).  So every iteration but the wave's last two (the drain after the
+    //      main loop) runs 64 tokens, and short keys never take the medium-key body (C2: 2 short +
+    //      1 mixed iteration per step before, ~2.3 short + ~0.3 medium now).
+    //      They are carried raw - the list entry and the aligned key dwords, which must be read
+    //      in their own step (the next one overwrites the staging bytes) - and decoded (byte
+    //      masks, length tag, hash) once, at the top of the iteration that probes them: decoded
+    //      at the read, every step decoded one short and one medium batch more than it counted
+    //      (C2: 3.33 and 1.29 decodes per step for 2.33 and 0.29 iterations)
+    u32 ces = 0, cem = 0;                 // carried entries (cem: 0 = no medium key in this lane)
+    uint3 cks = make_uint3(0, 0, 0);
+    KeyWords ckm{0, 0, 0, 0, 0};
     u32 ncs = 0, ncm = 0;                 // carried short / medium tokens (wave-uniform)
     // A miss reserves its units with an LDS atomic whose result is read one iteration later (after
     // that iteration's probe reads have returned, so the reservation adds no round trip of its
@@ -1358,9 +1371,10 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
 
         // ---- tokens: uniform iterations of 64 tokens, the short list first, then the medium/long
         //      one, each software-pipelined so that one LDS round trip per iteration carries this
-        //      token's table probe, the next token's key bytes and the entry after that; decodes
+        //      token's table probe, the next token's key bytes and the entry after that; reads
         //      past a list's end are unconditional (entries read other LDS words, key reads stay
-        //      inside the wave's staging bytes) and only the carried lanes' ones are used
+        //      inside the wave's staging bytes) and only the carried lanes' ones are used.
+        //      Nothing is decoded here: a batch is decoded by the iteration that probes it
         const u32 ts = tot_s, tm = tot >> 16;
         const u32 ns = ncs + ts, nfs = ns >> 6;          // short tokens; full iterations
         const u32 nm = ncm + tm, nfm = nm >> 6;          // medium/long tokens; full iterations
@@ -1376,33 +1390,37 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         {
             const uint3 kws = keyread_s(es0);
             const KeyWords kwm = keyread(em0);
-            const TokS t = decode_s(es0, kws);
-            const TokM u = decode_m(em0, lm < tm, kwm, wbase);
-            if ((u32)lane >= ncs) cs = t;
-            if ((u32)lane >= ncm) cm = u;
+            const u32 em = take_m(em0, lm < tm, wbase);
+            if ((u32)lane >= ncs) { ces = es0; cks = kws; }
+            if ((u32)lane >= ncm) { cem = em; ckm = kwm; }
         }
         stamp(4);
-        if (ABL == 2) { asm volatile("" ::"v"(cs.h), "v"(cm.h), "v"(e_nxt), "v"(f_nxt)); ncs = ns & 63; ncm = nm & 63; return 0; }
+        if (ABL == 2) {
+            asm volatile("" ::"v"(ces), "v"(cks.x), "v"(cks.y), "v"(cks.z), "v"(e_nxt));
+            asm volatile("" ::"v"(cem), "v"(ckm.d0), "v"(ckm.d1), "v"(ckm.d2), "v"(ckm.d3), "v"(ckm.d4), "v"(f_nxt));
+            ncs = ns & 63; ncm = nm & 63;
+            return 0;
+        }
         for (u32 it = 0; it < nfs; it++) {
+            const TokS cs = decode_s(ces, cks);
             const auto pr = tab.probe_short(cs.h);
             const uint3 nks = keyread_s(e_nxt);
             const u32 e_nn = ps[64 * (it + 2)];
             __builtin_amdgcn_sched_barrier(0);  // all three reads issue before the probe's wait
+            ces = e_nxt; cks = nks;           // the last iteration's: the raw leftover
+            e_nxt = e_nn;
             if (ABL == 3) {                   // probe reads and decodes, no table update or miss
-                asm volatile("" ::"v"(pr.x1), "v"(pr.x2));
-                cs = decode_s(e_nxt, nks);
-                e_nxt = e_nn;
+                asm volatile("" ::"v"(pr.x1), "v"(pr.x2), "v"(cs.k));
                 continue;
             }
             const bool hit = tab.finish_short(cs.k, cs.h, pr);
             hits_w += (u64)__popcll(__ballot(hit));
             store_pending(false);             // short keys: one unit
             miss_short(!hit, cs);
-            cs = decode_s(e_nxt, nks);
-            e_nxt = e_nn;
         }
         ncs = ns & 63;
         for (u32 it = 0; it < nfm; it++) {
+            const TokM cm = decode_m(cem, ckm);
             const auto pr = tab.probe(true, cm.h);
             const KeyWords nkw = keyread(f_nxt);
             const u32 f_nn = pm[64 * (it + 2)];
@@ -1411,11 +1429,12 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
             hits_w += (u64)__popcll(__ballot(hit));
             store_pending(true);              // the previous iteration's miss units
             miss_medium(cm.valid && !hit, cm);
-            cm = decode_m(f_nxt, lm + 64 * (it + 1) < tm, nkw, wbase);
+            cem = take_m(f_nxt, lm + 64 * (it + 1) < tm, wbase);
+            ckm = nkw;
             f_nxt = f_nn;
         }
         ncm = nm & 63;
-        u32 nst = nfs + 2 * nfm;
+        u32 nst = (ABL == 3 ? 0u : nfs) + 2 * nfm;   // ABL 3's short iterations store nothing
         if (nfm) {                            // a medium miss does not stay pending (a short
             store_pending(true);              // iteration stores one unit)
             missp = false;
@@ -1668,6 +1687,8 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         process(st, load_chunk(a.in, a.n, (long)(st * MAP_STEP) - 16 + 16 * lane));
 #if !WCG_DIRECT
     if (ABL == 0 || ABL >= 6) {           // the carried partial iterations
+        const TokS cs = decode_s(ces, cks);
+        const TokM cm = decode_m(cem, ckm);
         const auto pr = tab.probe_short(cs.h);
         const auto pm = tab.probe(true, cm.h);
         const bool vs = (u32)lane < ncs;

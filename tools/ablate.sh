@@ -1,6 +1,7 @@
 #!/bin/bash
-# k_map ablation timings (measurement only): WCG_MAP_ABLATE = 0 full, 1 tokenize only,
-# 2 + key extraction/hash, 3 + LDS lookups (misses dropped)
+# k_map ablation timings (measurement only): WCG_MAP_ABLATE = 0 full, 5 input loads, 4 + staging
+# and masks, 1 + start lists, 2 + the per-step first-entry reads and merges, 3 + the short-key
+# decodes and probes (misses dropped); the levels are described above utf8_mask_list in wcg_map.h
 for A in ${ABLATIONS:-0 1 2 3}; do
   WCG_MAP_ABLATE=$A python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-verify --no-end-to-end "$@" > /tmp/abl_$A.json || exit $?
   python3 - "$A" <<'PY'
