@@ -88,6 +88,11 @@ WCG_API int wcg_map(wcg_ctx *ctx, const uint8_t *host_bytes, uint64_t n);
 /* Same, input already resident in device memory (n bytes at dev_bytes). Asynchronous. */
 WCG_API int wcg_map_device(wcg_ctx *ctx, const void *dev_bytes, uint64_t n);
 
+/* The size limit of one wcg_map_device call (pure arithmetic, no device): the map kernel counts
+ * its 992-byte steps in 32 bits, so a split of about 4 TB or more is WCG_EINVAL (wcg_map_device
+ * checks this before it looks at the pointer or the device); anything smaller is WCG_OK. */
+WCG_API int wcg_map_size_check(uint64_t n);
+
 /* Split (mapreduce.go:141-179) + DoMap x nMap over a whole input file, on the GPU: the file is
  * read by a pool of host threads into two pinned staging buffers and copied to HBM in
  * line-aligned chunks, each copy overlapping the map kernels of the previous chunk.  Split's

@@ -1376,13 +1376,25 @@ int wcg_reset(wcg_ctx* c) {
     return WCG_OK;
 }
 
+// k_map indexes its 992-byte wave steps with 32 bits (wave-uniform step arithmetic stays on the
+// scalar unit); a wave looks MAP_SETS strides past its current step, so the last 2^24 indices stay
+// free (a stride is G * 16 steps)
+static constexpr u64 MAP_STEP_HEADROOM = 1ull << 24;
+int wcg_map_size_check(uint64_t n) {
+    const u64 steps = n / MAP_STEP + (n % MAP_STEP != 0);
+    return steps > 0xFFFFFFFFull - MAP_STEP_HEADROOM ? WCG_EINVAL : WCG_OK;
+}
+
 int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
     if (!c) return WCG_EINVAL;
     c->pending = false;
     if (n == 0) return WCG_OK;
+    if (wcg_map_size_check(n) != WCG_OK) { c->err = "wcg_map_device: more wave steps than k_map's 32-bit step index holds"; return WCG_EINVAL; }
     if (!dev_bytes || ((uintptr_t)dev_bytes & 15)) { c->err = "wcg_map_device: input must be 16-byte aligned"; return WCG_EINVAL; }
     int rc = set_dev(c);
     if (rc) return rc;
+    // the steps a wave prefetches past the last one stay inside the index's headroom
+    if ((u64)c->ncu * MAP_WGS * MAP_WAVES * (MAP_SETS + 1) > MAP_STEP_HEADROOM) { c->err = "wcg_map_device: grid too large"; return WCG_EINVAL; }
     MapArgs a;
     a.in = (const uint8_t*)dev_bytes;
     a.n = n;

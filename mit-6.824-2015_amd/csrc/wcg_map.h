@@ -99,7 +99,8 @@ template <bool SPLIT> __device__ __forceinline__ u32 short_bucket(u32 h) { retur
 template <bool SPLIT> __device__ __forceinline__ u32 medium_bucket(u32 h) {
     return SPLIT ? (h & (MISS_SHORT_BUCKETS / 2 - 1)) + MISS_SHORT_BUCKETS : (h & (MISS_SHORT_BUCKETS - 1));
 }
-constexpr u32 SST_LEN_SHIFT = 10;            // start entry = window offset | min(run, 16) << 10
+constexpr u32 SST_LEN_SHIFT = 10;            // start entry = window offset | length field << 10: medium
+                                             // list min(run, 16), short list 8 * run (<= 56)
 
 struct MapArgs {
     const uint8_t* in;
@@ -1155,14 +1156,25 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
     // Steps are dealt chip-wide: wave w of workgroup g takes steps (g * 16 + w) + k * G * 16, so
     // the chip sweeps the input front to back (HBM-friendly) while every workgroup still sees
     // a uniform sample of it for its LDS table.
-    const u64 nsteps = a.ntiles;
-    const u64 stride = (u64)gridDim.x * MAP_WAVES;
+    // step indices are 32-bit (the host rejects a call with more steps): a wave's step, the step
+    // count and the stride are wave-uniform, and the scalar unit has no ordered 64-bit compare -
+    // as u64 every `step < nsteps` was two v_mov_b64 and a v_cmp_*_u64 on the vector unit
+    const u32 nsteps = (u32)a.ntiles;
+    const u32 stride = gridDim.x * MAP_WAVES;
+    // the first step whose 1 KiB window passes the input's end (step * 992 + 1008 > n): that
+    // step and the later ones are the byte-exact tail steps.  nsteps - 2 <= ntail <= nsteps
+    u32 ntail = nsteps;
+    while (ntail != 0 && (u64)(ntail - 1) * MAP_STEP + (MAP_WIN - 16) > a.n) ntail--;
     // window chunk c <-> input bytes [step base - 16 + 16c, +16); lane c holds chunk c
-    u64 my_tokens = 0;                           // wave-uniform (WCG_DIRECT: per lane)
+    // (32-bit: a wave's share of a call's < 2^32 steps stays far below 2^32 tokens)
+    u32 my_tokens = 0;                           // wave-uniform (WCG_DIRECT: per lane)
     // token starts are owned by lanes 1-62 only (lane 0: the prefix chunk, 63: the look-ahead)
     const u32 own16 = (u32)(lane - 1) < (u32)MAP_OWN ? 0xFFFFu : 0u;
+    // hits: a per-lane add under the hit mask.  Counted per wave (popcount of the hit ballot) the
+    // lane mask that leaves the insert branch was first turned into 0/1 and compared again for
+    // the ballot: two vector instructions and three scalar ones per iteration, and a 64-bit
+    // scalar sum held across every step
     u32 my_hits = 0, my_global = 0, my_long = 0;
-    u64 hits_w = 0;                              // wave-uniform: hits counted from the hit masks (SALU)
 
     // miss-log stores of this workgroup: one buffer resource over its regions
     const u32 P = a.pmask + 1;
@@ -1173,11 +1185,15 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
     // (at the input start for step 0, whose prefix chunk is out of range and reads zeros).
     // Every prefetch is unconditional: steps past the end load offset 0xFFFFFFF0, which reads
     // zeros without touching memory.
-    auto addr = [&](u64 step, v4i& rsrc, u32& om) {
+    auto addr = [&](u32 step, v4i& rsrc, u32& om) {
         const bool live = step < nsteps;
-        const u64 org = (step == 0 || !live) ? 0 : step * MAP_STEP - 16;
+        const u64 org = (step == 0 || !live) ? 0 : (u64)step * MAP_STEP - 16;   // s_mul_i32 + s_mul_hi_u32
         const u64 span = live ? a.n - org : 0;
-        const u32 nrec = span > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)span;
+        // the high word tested on its own, behind an empty asm: the compiler folds the test back
+        // into `span > 0xFFFFFFFF`, a v_cmp_lt_u64 on the vector unit
+        u32 span_hi = (u32)(span >> 32);
+        asm("" : "+s"(span_hi));
+        const u32 nrec = span_hi != 0 ? 0xFFFFFFFFu : (u32)span;
         rsrc = make_rsrc(a.in + org, nrec);
         const u32 rel = step == 0 ? 0u : 16u;
         om = live ? 16 * lane + rel - 16 : OOB;                  // step 0, lane 0: wraps to OOB
@@ -1196,11 +1212,11 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         return make_uint3(q[0], q[1], q[2]);
     };
     auto decode_s = [&](u32 e, const uint3& kw) -> TokS {
-        const u32 rp = e & ((1u << SST_LEN_SHIFT) - 1), len = e >> SST_LEN_SHIFT;
+        const u32 rp = e & ((1u << SST_LEN_SHIFT) - 1), len8 = e >> SST_LEN_SHIFT;   // 8 * len
         const u32 bsh = rp & 3u;
         const u64 w = (u64)__builtin_amdgcn_alignbyte(kw.z, kw.y, bsh) << 32 | __builtin_amdgcn_alignbyte(kw.y, kw.x, bsh);
         TokS t;
-        t.k = (w & ((1ull << (8 * len)) - 1)) | (u64)len << 56;
+        t.k = (w & ((1ull << len8) - 1)) | (u64)len8 << 53;
         t.h = lds_hash32((u32)t.k, (u32)(t.k >> 32), 0u, 0u);
         return t;
     };
@@ -1214,9 +1230,11 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
     // bytes) is measured and logged here, while its step's window masks are in LDS (the entry may
     // be carried to the next step), and takes no part in the table; a lane past the list's end
     // keeps entry 0.  Either way the length field is outside 8..15, which is what decode_m tests
-    auto take_m = [&](u32 e, bool act, long wbase) -> u32 {
+    // (step: the entry's step; the window's 64-bit input offset is formed here, where it is used)
+    auto take_m = [&](u32 e, bool act, u32 step) -> u32 {
         if (act && (e >> SST_LEN_SHIFT) >= 16) {
             const u32 rp = e & ((1u << SST_LEN_SHIFT) - 1);
+            const long wbase = (long)((u64)step * MAP_STEP) - 16;   // input offset of window byte 0
             my_long++;
             if (ABL != 6) long_token_log<ABL>(a, (u64)(wbase + rp), rp, wmask[wave], &lcur);
         }
@@ -1272,7 +1290,8 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
             u64* r = wpool + (u64)pp * a.region_cap;
             for (u32 k = posp; k < rcap; k++) r[k] = 0;
             my_global++;
-            ginsert(a.gtab, a.gmask, k0p, k1p, gslot(key_hash(k0p, k1p)), 1, a.st);
+            const u64 k1 = nup == 2 ? k1p : 0;   // a short miss leaves k1p as it was
+            ginsert(a.gtab, a.gmask, k0p, k1, gslot(key_hash(k0p, k1)), 1, a.st);
         }
     };
     auto miss_short = [&](bool miss, const TokS& t) {
@@ -1280,8 +1299,8 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         pp = short_bucket<SPLIT>(t.h);
         nup = 1u;
         posp = atomicAdd(&cursor[pp], miss ? 1u : 0u);   // every lane (0 = no miss)
-        k0p = t.k; k1p = 0;
-    };
+        k0p = t.k;                        // k1p is not zeroed (a move per iteration): a one-unit
+    };                                    // miss's second store is dropped, whatever it holds
     auto miss_medium = [&](bool miss, const TokM& t) {
         missp = miss;
         pp = medium_bucket<SPLIT>(t.h);
@@ -1291,8 +1310,7 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
     };
 
     // one step: returns the number of unit stores it issued (prefetch accounting)
-    auto process = [&](u64 step, const uint4 mine) -> u32 {
-        const long wbase = (long)(step * MAP_STEP) - 16;        // input offset of window byte 0
+    auto process = [&](u32 step, const uint4 mine) -> u32 {
         if (ABL == 5) { asm volatile("" ::"v"(mine.x)); return 0; }
         reinterpret_cast<uint4*>(bytes)[lane] = mine;
         // ---- letter mask of the lane's chunk (lane 0: only bit 15 is used - the predecessor of
@@ -1352,12 +1370,16 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         auto list = [&](uint16_t* w, u32 msk, bool shrt) {
 #pragma unroll
             for (int k = 0; k < 8; k++) {                   // <= 8 starts per 16-byte chunk
-                if (__ballot(msk != 0) == 0) break;
-                if (msk) {
-                    const u32 b = __builtin_ctz(msk);
-                    msk &= msk - 1;
+                const u32 cur = msk;
+                if (__ballot(cur != 0) == 0) break;
+                // every lane drops its lowest start (a lane without one keeps 0): updated inside
+                // the branch, msk cost a compare's twin and a zeroing move per slot to leave it
+                msk &= msk - 1;
+                if (cur) {
+                    const u32 b = __builtin_ctz(cur);
                     const u32 run = __builtin_ctz(~(w32 >> b));   // >= 1; 32 - b when the window is all letters
-                    const u32 len = shrt ? run : (run < 16 ? run : 16u);   // 16 = long token (> 15 bytes)
+                    // short entries hold 8 * len (<= 56: the field is 6 bits), what decode_s shifts by
+                    const u32 len = shrt ? 8 * run : (run < 16 ? run : 16u);   // 16 = long token (> 15 bytes)
                     w[k] = (uint16_t)((lbase + b) | (len << SST_LEN_SHIFT));
                 }
             }
@@ -1390,7 +1412,7 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         {
             const uint3 kws = keyread_s(es0);
             const KeyWords kwm = keyread(em0);
-            const u32 em = take_m(em0, lm < tm, wbase);
+            const u32 em = take_m(em0, lm < tm, step);
             if ((u32)lane >= ncs) { ces = es0; cks = kws; }
             if ((u32)lane >= ncm) { cem = em; ckm = kwm; }
         }
@@ -1414,7 +1436,7 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
                 continue;
             }
             const bool hit = tab.finish_short(cs.k, cs.h, pr);
-            hits_w += (u64)__popcll(__ballot(hit));
+            my_hits += (u32)hit;
             store_pending(false);             // short keys: one unit
             miss_short(!hit, cs);
         }
@@ -1426,10 +1448,10 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
             const u32 f_nn = pm[64 * (it + 2)];
             __builtin_amdgcn_sched_barrier(0);
             const bool hit = tab.finish(cm.valid, true, cm.k0, cm.k1, cm.h, pr);
-            hits_w += (u64)__popcll(__ballot(hit));
+            my_hits += (u32)hit;
             store_pending(true);              // the previous iteration's miss units
             miss_medium(cm.valid && !hit, cm);
-            cem = take_m(f_nxt, lm + 64 * (it + 1) < tm, wbase);
+            cem = take_m(f_nxt, lm + 64 * (it + 1) < tm, step);
             ckm = nkw;
             f_nxt = f_nn;
         }
@@ -1458,8 +1480,8 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
     //      the lane with the most such starts has (C2: 4.2 per step for all starts).
     struct TokS { u64 k; u32 h; };
     struct TokG { u64 k0, k1; u32 h; bool lng; };
-    auto process = [&](u64 step, const uint4 mine) -> u32 {
-        const long wbase = (long)(step * MAP_STEP) - 16;        // input offset of window byte 0
+    auto process = [&](u32 step, const uint4 mine) -> u32 {
+        const long wbase = (long)((u64)step * MAP_STEP) - 16;   // input offset of window byte 0
         // the next chunk's dwords by DPP wave_shl:1 (all lanes active; lane 63 gets zeros)
         const u32 D0 = mine.x, D1 = mine.y, D2 = mine.z, D3 = mine.w;
         const u32 D4 = (u32)__builtin_amdgcn_update_dpp(0, (int)mine.x, 0x130, 0xF, 0xF, false);
@@ -1638,11 +1660,13 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
 
     // ---- main loop, unrolled over the register sets so that each set's load and waits name
     //      fixed registers (tools/check_inflight.py); a set's load was issued MAP_SETS steps
-    //      earlier; h1..h3 = unit stores of the last three steps (the wait count)
-    auto is_tail = [&](u64 step) { return step * MAP_STEP - 16 + MAP_WIN > a.n; };
+    //      earlier; hq = unit stores of the last three steps, a byte each (the wait count;
+    //      a step issues at most 26; one scalar register across process(), not three).  The
+    //      count enters through readfirstlane: it is wave-uniform, but the wait's "s" operand
+    //      must not depend on the compiler proving that through the loop's phis
     auto u4 = [](v4u v) { return make_uint4(v.x, v.y, v.z, v.w); };
     v4u mA, mB, mC, mD;
-    u64 st = (u64)blockIdx.x * MAP_WAVES + wave;
+    u32 st = blockIdx.x * MAP_WAVES + (u32)wave;
     {
         v4i r; u32 om;
         addr(st, r, om);              set_load_A(r, om, mA);
@@ -1652,20 +1676,21 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
             addr(st + 3 * stride, r, om); set_load_D(r, om, mD);
         }
     }
-    u32 h1 = 0, h2 = 0, h3 = 0;
+    u32 hq = 0;
 #define WCG_MAP_STEP(S)                                                                         \
     {                                                                                           \
-        if (st >= nsteps || is_tail(st)) break;                                                 \
+        if (st >= ntail) break;                                                                 \
         v4i r; u32 om;                                                                          \
         addr(st + MAP_SETS * stride, r, om);                                                    \
         stamp(0);                                                                               \
         if (WCG_NOWAIT) set_wait_##S(63, m##S); /* diagnostics only: results are wrong */       \
         else if (WCG_WAIT0) set_wait_##S(0, m##S);                                              \
-        else set_wait_##S((MAP_SETS - 1) + h1 + (MAP_SETS == 4 ? h2 + h3 : 0), m##S);           \
+        else set_wait_##S((MAP_SETS - 1) + (hq & 0xFFu) +                                       \
+                          (MAP_SETS == 4 ? ((hq >> 8) & 0xFFu) + ((hq >> 16) & 0xFFu) : 0), m##S);   \
         stamp(1);                                                                               \
         const u32 it_ = process(st, u4(m##S));                                                  \
         set_load_##S(r, om, m##S);                                                              \
-        h3 = h2; h2 = h1; h1 = it_;                                                             \
+        hq = (hq << 8) | (u32)__builtin_amdgcn_readfirstlane((int)it_);                        \
         st += stride;                                                                           \
     }
     while (true) {
@@ -1684,7 +1709,7 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         set_wait_n_D<0>(mD);
     }
     for (; st < nsteps; st += stride)     // tail steps: byte-exact reloads
-        process(st, load_chunk(a.in, a.n, (long)(st * MAP_STEP) - 16 + 16 * lane));
+        process(st, load_chunk(a.in, a.n, (long)((u64)st * MAP_STEP) - 16 + 16 * lane));
 #if !WCG_DIRECT
     if (ABL == 0 || ABL >= 6) {           // the carried partial iterations
         const TokS cs = decode_s(ces, cks);
@@ -1728,7 +1753,7 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
     // to DevState).  Per-wave atomics on DevState cost ~12 ns each serialised on one line:
     // 16K of them added 0.2 ms to every launch.
     __shared__ u64 wsum[MAP_WAVES][4];
-    u64 v0 = (WCG_DIRECT || lane == 0) ? my_tokens : 0, v1 = my_hits + (lane == 0 ? hits_w : 0), v2 = my_global, v3 = my_long;
+    u64 v0 = (WCG_DIRECT || lane == 0) ? my_tokens : 0u, v1 = my_hits, v2 = my_global, v3 = my_long;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         v0 += __shfl_xor(v0, d, 64); v1 += __shfl_xor(v1, d, 64);

@@ -27,7 +27,7 @@ EXPORTED = [
     "wcg_export_write", "wcg_merge_runs", "wcg_result_copy_device", "wcg_sync", "wcg_free",
     "wcg_comm_id", "wcg_comm_init", "wcg_exchange", "wcg_gather_merge", "wcg_exchange_plan",
     "wcg_gather_plan", "wcg_exchange_local", "wcg_gather_merge_local", "wcg_reduce_path",
-    "wcg_reduce_async", "wcg_reduce_wait", "wcg_ingest_stats", "wcg_top",
+    "wcg_reduce_async", "wcg_reduce_wait", "wcg_ingest_stats", "wcg_top", "wcg_map_size_check",
 ]
 COMM_ID_BYTES = 128
 TOP_MAX = 1024                            # WCG_TOP_MAX
@@ -91,6 +91,7 @@ def load() -> ctypes.CDLL:
         "wcg_reduce_wait": (I, [P, PU64, PU64]),
         "wcg_ingest_stats": (I, [P, ctypes.POINTER(ctypes.c_double), I]),
         "wcg_top": (I, [P, U32, P, U64, PU64, PU64]),
+        "wcg_map_size_check": (I, [U64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
