@@ -155,17 +155,22 @@ __device__ __forceinline__ u32 ascii_mask4(u32 x) {
     u32 hi = a & ~b & 0x80808080u;
     return (((hi >> 7) * 0x00204081u) >> 21) & 0xFu;
 }
-// 16 ASCII bytes -> letter mask.  The letter flags sit in bit 7 of each byte; one multiply by
-// 2^0 + 2^7 + 2^14 + 2^21 gathers the four flags of a dword into bits 28-31 (the partial
-// products land on distinct bits: no carries), and each nibble is shifted straight to its place
+// 16 ASCII bytes -> letter mask.  The letter flags sit in bit 7 of each byte (0x80 or 0), and
+// v_dot4_u32_u8 sums a dword's four flag bytes with the weights 1, 2, 4, 8 (16 .. 128 for the next
+// dword, accumulated into the same sum): 128 * the 8-bit mask of two dwords, at most 0x80 * 255,
+// with no shift, and or mask per dword (a multiply by 2^0 + 2^7 + 2^14 + 2^21 gathered each
+// dword's flags before; v_dot4_u32_u8 issues at v_mul_lo_u32's rate, and k_map issues 5 VALU
+// fewer per step: DESIGN.md section 19)
 __device__ __forceinline__ u32 ascii_hi4(u32 x) {
     const u32 t = x | 0x20202020u;
     return (t + 0x1F1F1F1Fu) & ~(t + 0x05050505u) & 0x80808080u;   // >= 'a' and < '{'
 }
 __device__ __forceinline__ u32 ascii_mask16(uint4 v) {
-    constexpr u32 G = 0x00204081u;
-    return ((ascii_hi4(v.x) * G) >> 28) | (((ascii_hi4(v.y) * G) >> 24) & 0xF0u) |
-           (((ascii_hi4(v.z) * G) >> 20) & 0xF00u) | (((ascii_hi4(v.w) * G) >> 16) & 0xF000u);
+    u32 a = __builtin_amdgcn_udot4(ascii_hi4(v.x), 0x08040201u, 0u, false);
+    a = __builtin_amdgcn_udot4(ascii_hi4(v.y), 0x80402010u, a, false);
+    u32 b = __builtin_amdgcn_udot4(ascii_hi4(v.z), 0x08040201u, 0u, false);
+    b = __builtin_amdgcn_udot4(ascii_hi4(v.w), 0x80402010u, b, false);
+    return (a >> 7) | (b << 1);                   // < 0x10000
 }
 __device__ __forceinline__ bool all_ascii(uint4 v) { return ((v.x | v.y | v.z | v.w) & 0x80808080u) == 0; }
 

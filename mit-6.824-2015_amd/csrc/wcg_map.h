@@ -1173,7 +1173,10 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
     // hits: a per-lane add under the hit mask.  Counted per wave (popcount of the hit ballot) the
     // lane mask that leaves the insert branch was first turned into 0/1 and compared again for
     // the ballot: two vector instructions and three scalar ones per iteration, and a 64-bit
-    // scalar sum held across every step
+    // scalar sum held across every step.  (Taken off the miss cursors after the main loop
+    // instead - hits = tokens - long tokens - misses - the add and its select leave the
+    // iterations, but the hit mask then costs two more scalar instructions per iteration and the
+    // kernel's cycles do not move: DESIGN.md section 19.)
     u32 my_hits = 0, my_global = 0, my_long = 0;
 
     // miss-log stores of this workgroup: one buffer resource over its regions
@@ -1317,10 +1320,15 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         //      the step's first byte; lane 63: only as the successor of chunk 62, and on the
         //      UTF-8 path its last 3 bits, whose runes may end past the window, are forced to
         //      letters, so a run reaching them is measured exactly by the long-token path)
-        // the next chunk's first dword by DPP (all lanes active; lane 63 gets zeros)
-        const u32 nx = (u32)__builtin_amdgcn_update_dpp(0, (int)mine.x, 0x130, 0xF, 0xF, false);   // wave_shl:1
+        // the next chunk's first dword by DPP (all lanes active; bound_ctrl: lane 63, which has
+        // no source lane, reads zeros from the instruction itself - with it off the compiler
+        // zeroes the destination first, a v_mov_b32 per shift)
+        const u32 nx = (u32)__builtin_amdgcn_update_dpp(0, (int)mine.x, 0x130, 0xF, 0xF, true);   // wave_shl:1
         u32 m;
 #if WCG_UTF8_LIST
+        // wave-uniform branch.  Neither side leaves bits above 15: ascii_mask16 has none, and the
+        // list form ORs a rune's bytes in the next chunk into that chunk's word in LDS and returns
+        // the 16-bit word, so no rune carry is merged here (it was the identity on every step)
         if (__ballot(!all_ascii(mine)) == 0) {
             m = ascii_mask16(mine);
         } else {
@@ -1334,15 +1342,16 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
             m = utf8_mask_lds(mine, nx, lt);
             if (lane == 63) m |= 0xE000u;
         }
+        // bytes of this chunk covered by a letter rune that started in the previous chunk (the
+        // branch above is per lane: the shift runs with all lanes active, after it)
+        m = (m | ((u32)__builtin_amdgcn_update_dpp(0, (int)(m >> 16), 0x138, 0xF, 0xF, true) & 7u)) & 0xFFFFu;
 #endif
-        // bytes of this chunk covered by a letter rune that started in the previous chunk
-        m = (m | ((u32)__builtin_amdgcn_update_dpp(0, (int)(m >> 16), 0x138, 0xF, 0xF, false) & 7u)) & 0xFFFFu;
         if (ABL == 4) { asm volatile("" ::"v"(m)); return 0; }
         wmask[wave][lane] = (uint16_t)m;
         stamp(2);
-        // neighbours' masks by DPP lane shifts
-        const u32 prevm = (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x138, 0xF, 0xF, false);   // wave_shr:1
-        const u32 nextm = (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x130, 0xF, 0xF, false);   // wave_shl:1
+        // neighbours' masks by DPP lane shifts (bound_ctrl: lane 0 / lane 63 read 0)
+        const u32 prevm = (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x138, 0xF, 0xF, true);   // wave_shr:1
+        const u32 nextm = (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x130, 0xF, 0xF, true);   // wave_shl:1
         u32 starts = m & ~((m << 1) | (prevm >> 15)) & own16;
         const u32 w32 = m | (nextm << 16);
         // Start list, short keys (<= 7 bytes: 89% of C2 tokens) first, then the others: a start
@@ -1367,6 +1376,11 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
         // two offsets per start: 15 VALU per iteration against 9 here, for max(all) = 4.2
         // iterations per step against max(short) + max(other) = 4.2 + 1.6 (C2)
         const u32 lbase = 16 * lane;
+        // a short start has a non-letter within 8 bits above it and b <= 15, so the zeros that a
+        // shift brings in at the top are never reached: its run length is read off the inverted
+        // window, inverted once per step (the medium list's all-letters case needs the stop that
+        // inverting after the shift puts at bit 32 - b)
+        const u32 nw32 = ~w32;
         auto list = [&](uint16_t* w, u32 msk, bool shrt) {
 #pragma unroll
             for (int k = 0; k < 8; k++) {                   // <= 8 starts per 16-byte chunk
@@ -1377,7 +1391,8 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
                 msk &= msk - 1;
                 if (cur) {
                     const u32 b = __builtin_ctz(cur);
-                    const u32 run = __builtin_ctz(~(w32 >> b));   // >= 1; 32 - b when the window is all letters
+                    // >= 1; medium list: 32 - b when the window is all letters
+                    const u32 run = shrt ? __builtin_ctz(nw32 >> b) : __builtin_ctz(~(w32 >> b));
                     // short entries hold 8 * len (<= 56: the field is 6 bits), what decode_s shifts by
                     const u32 len = shrt ? 8 * run : (run < 16 ? run : 16u);   // 16 = long token (> 15 bytes)
                     w[k] = (uint16_t)((lbase + b) | (len << SST_LEN_SHIFT));

@@ -29,6 +29,8 @@ __global__ __launch_bounds__(1024) void k_valu(unsigned* out, unsigned long long
 #define CMP32(i) asm volatile("v_cmp_eq_u32 vcc, %0, %1\n\tv_cndmask_b32 %0, %0, %1, vcc" : "+v"(v##i) : "v"(m) : "vcc");
 #define BFE(i) asm volatile("v_bfe_u32 %0, %0, 3, 7" : "+v"(v##i));
 #define ADD64(i) asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(w##i) : "v"(w1));
+#define DOT4(i) asm volatile("v_dot4_u32_u8 %0, %0, %1, %0" : "+v"(v##i) : "v"(m));
+#define WSHR(i) asm volatile("v_mov_b32_dpp %0, %0 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0" : "+v"(v##i));
         if (K == 0) { OPS32(A32) }
         if (K == 1) { OPS32(M32) }
         if (K == 2) { OPS32(M24) }
@@ -39,6 +41,8 @@ __global__ __launch_bounds__(1024) void k_valu(unsigned* out, unsigned long long
         if (K == 7) { OPS32(CMP32) }
         if (K == 8) { OPS32(BFE) }
         if (K == 9) { OPS32(ADD64) }
+        if (K == 10) { OPS32(DOT4) }
+        if (K == 11) { OPS32(WSHR) }
     }
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
     if (threadIdx.x == 0) cyc[blockIdx.x] = t1 - t0;
@@ -85,5 +89,7 @@ int main() {
     run<7>("cmp32+cnd", 2, out, cyc, ncu);
     run<8>("bfe", 1, out, cyc, ncu);
     run<9>("add64", 1, out, cyc, ncu);
+    run<10>("dot4_u8", 1, out, cyc, ncu);
+    run<11>("dpp_wshr", 1, out, cyc, ncu);
     return 0;
 }
