@@ -166,6 +166,32 @@ WCG_API int wcg_partition_all(wcg_ctx *ctx, uint32_t nreduce, uint8_t *host_out,
 WCG_API int wcg_top(wcg_ctx *ctx, uint32_t n, uint8_t *host_out, uint64_t cap, uint64_t *nlines,
                     uint64_t *nbytes);
 
+/* "How often does this word occur?"  counts[i] = the count of key i in the last wcg_reduce()'s
+ * result, 0 if it does not occur: a binary search per key over the sorted records on the device,
+ * so only the counts cross to the host.  Key i is the bytes keys[key_off[i] .. key_off[i+1])
+ * (key_off has nq + 1 entries, non-decreasing, key_off[0] == 0; otherwise WCG_EINVAL).  Any bytes
+ * are allowed: an empty key, a key holding a NUL or 0xFF byte or a non-letter simply does not
+ * occur.  nq == 0 is WCG_OK and touches nothing.  State rules as wcg_top's: WCG_ESTATE before a
+ * wcg_reduce() (a pending wcg_reduce_async job is waited for), after wcg_free of its result and
+ * after wcg_merge_runs / wcg_gather_merge*; the result calls, wcg_partition*, wcg_export*, wcg_top,
+ * wcg_stats and wcg_timings in between do not disturb it.  After wcg_exchange every key has one
+ * owner, so a word's count over all ranks is the sum of the ranks' lookups. */
+WCG_API int wcg_lookup(wcg_ctx *ctx, const uint8_t *keys, const uint64_t *key_off, uint64_t nq,
+                       uint64_t *counts);
+
+/* The same with keys, offsets and counts in device memory; asynchronous on the context's stream
+ * (the offsets are not checked). */
+WCG_API int wcg_lookup_device(wcg_ctx *ctx, const void *dev_keys, const void *dev_key_off, uint64_t nq,
+                              void *dev_counts);
+
+/* The lines "key: count\n" of the merged file with lo <= key < hi (bytewise), in file order,
+ * found and formatted on the device.  lo == NULL: from the first line; hi == NULL: to the last.
+ * lo >= hi: no lines (WCG_OK).  *nlines / *nbytes are always set; host_out == NULL queries them
+ * only (the lines stay cached on the device until the next job, so a second call whose bounds
+ * select the same lines is a copy); cap < *nbytes: WCG_EINVAL.  State rules as wcg_lookup's. */
+WCG_API int wcg_range(wcg_ctx *ctx, const uint8_t *lo, uint64_t lo_len, const uint8_t *hi, uint64_t hi_len,
+                      uint8_t *host_out, uint64_t cap, uint64_t *nlines, uint64_t *nbytes);
+
 /* DoMap's reference-exact intermediate files (mapreduce.go:214-230) for one split: for every
  * token, in input order, the line {"Key":"tok","Value":"1"}\n in file ihash(tok) % nreduce - the
  * bytes the reference's json.Encoder writes to mrtmp.<f>-<m>-<r>, so an unmodified CPU DoReduce

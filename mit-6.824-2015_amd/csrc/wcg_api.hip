@@ -30,6 +30,7 @@
 #include "wcg_agg.h"
 #include "wcg_reduce.h"
 #include "wcg_top.h"
+#include "wcg_query.h"
 #include "wcg_fused.h"
 #include "wcg_ingest.h"
 
@@ -105,6 +106,15 @@ struct wcg_ctx {
     u64* top_cand = nullptr; u64 top_cand_cap = 0;   // k_top_select's survivors (wcg_top.h: TOP_HDR + items)
     Rec* top_rec = nullptr; u64 top_rec_cap = 0;     // the chosen records, ascending
     uint8_t* d_top = nullptr; u64 top_cap = 0;       // their lines
+    // queries (wcg_lookup / wcg_range, wcg_query.h): staging of host queries, and the lines of
+    // the sorted records [range_a, range_b), valid while range_ok (reset wherever top_n is)
+    uint8_t* q_keys = nullptr; u64 q_keys_cap = 0;
+    u64* q_off = nullptr; u64 q_off_cap = 0;
+    u64* q_cnt = nullptr; u64 q_cnt_cap = 0;
+    u64* rs_part = nullptr; u64 rs_part_cap = 0;     // k_range_size's parts, then the two totals
+    bool range_ok = false;
+    u64 range_a = 0, range_b = 0, range_lines = 0, range_bytes = 0;
+    uint8_t* d_range = nullptr; u64 range_cap = 0;
     // c->sorted[0, sorted_n) still holds the last wcg_reduce's records (wcg_top reads them): set by
     // the reduce; the record buffers' reallocation (a later compaction that needs more) ends it
     bool sorted_live = false;
@@ -1147,7 +1157,7 @@ int wcg_close(wcg_ctx* c) {
                     c->llog, c->llog_len, c->smp, c->bid, c->spx, c->irec, c->lent, c->lpcur, c->spill, c->spill_len, c->pool2, c->rlen2, c->remit, c->ovf, c->hist, c->spart, c->ikey, c->iidx, c->groups,
                     c->pid, c->d_partb, c->nlpos, c->d_rb, c->d_b0, c->d_jin, c->d_jout, c->jhist, c->dbig,
                     c->d_xrow, c->xrecv, c->grecv, c->glist, c->llist, c->fr_buf, c->flist,
-                    c->top_cand, c->top_rec, c->d_top};
+                    c->top_cand, c->top_rec, c->d_top, c->q_keys, c->q_off, c->q_cnt, c->rs_part, c->d_range};
     if (c->comm) (void)ncclCommDestroy(c->comm);
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (c->h_x) (void)hipHostFree(c->h_x);
@@ -1282,7 +1292,7 @@ int reset_tables(wcg_ctx* c) {
     c->counts_clean = true;
     c->compacted = c->reduced = c->merged = false;
     c->exp_ready = false;
-    c->part_R = 0; c->top_n = 0;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false;
     c->nrec = 0;
     c->out_len = 0;
     c->two_pass_used = false;
@@ -1682,7 +1692,7 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
     c->map_launches_since_reset++;
     c->compacted = c->reduced = c->merged = false;
     c->exp_ready = false;
-    c->part_R = 0; c->top_n = 0;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false;
     return WCG_OK;
 }
 
@@ -1772,7 +1782,7 @@ int wcg_reduce(wcg_ctx* c, uint64_t* nkeys, uint64_t* nbytes) {
         }
         c->reduced = true;
         c->merged = false;
-        c->part_R = 0; c->top_n = 0;
+        c->part_R = 0; c->top_n = 0; c->range_ok = false;
         if (nkeys) *nkeys = c->nkeys;
         if (nbytes) *nbytes = c->out_len;
         return WCG_OK;
@@ -1818,7 +1828,7 @@ int wcg_reduce(wcg_ctx* c, uint64_t* nkeys, uint64_t* nbytes) {
     c->sorted_live = true;
     c->sorted_n = c->nrec;
     c->reduced = true;
-    c->part_R = 0; c->top_n = 0;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false;
     if (nkeys) *nkeys = c->nkeys;
     if (nbytes) *nbytes = c->out_len;
     return WCG_OK;
@@ -1842,7 +1852,7 @@ int wcg_reduce_async(wcg_ctx* c) {
     c->pending = true;
     c->reduced = true;
     c->merged = false;
-    c->part_R = 0; c->top_n = 0;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false;
     return WCG_OK;
 }
 
@@ -2027,6 +2037,136 @@ int wcg_top(wcg_ctx* c, uint32_t n, uint8_t* host_out, uint64_t cap, uint64_t* n
     return WCG_OK;
 }
 
+// wcg_top's state rules, for the calls that search the sorted records
+static int query_state(wcg_ctx* c, const char* who) {
+    RC(resolve(c));
+    const char* why = nullptr;
+    if (!c->reduced) why = " before wcg_reduce";
+    else if (c->merged) why = " after wcg_merge_runs (a merged file's records carry no counts)";
+    else if (!c->sorted_live) why = ": the sorted records were released (record buffers regrown); wcg_reduce again";
+    if (why) { c->err = std::string(who) + why; return WCG_ESTATE; }
+    return set_dev(c);
+}
+
+// k_lookup<MODE> over nq queries in device memory (the sorted records hold at least one)
+static int lookup_launch(wcg_ctx* c, int mode, const void* keys, const void* off, u64 nq, u64* out) {
+    // A workgroup per tile up to LK_MAXG (8 per CU of 256, more than are resident at once: a CU
+    // takes the next when one ends; each lane keeps LK_Q loads in flight).
+    // tests: WCG_LOOKUP_GRID may only lower the grid (a few thousand queries then give a workgroup
+    // many tiles); read on every call like WCG_TOP_GRID
+    u64 grid = std::min<u64>(cdiv(nq, LK_TILE), std::min<u64>(LK_MAXG, 8ull * (u64)std::max(1, c->ncu))), v;
+    if (cap_env("WCG_LOOKUP_GRID", &v)) grid = std::max<u64>(1, std::min(grid, v));
+    const auto* k = static_cast<const uint8_t*>(keys);
+    const auto* o = static_cast<const u64*>(off);
+    // batches of LK_LDS_MIN queries and more narrow their searches in LDS first.  tests:
+    // WCG_LOOKUP_LDS_MIN moves that threshold (1: every batch, a huge value: none), read on every call
+    u64 lds_min = LK_LDS_MIN;
+    if (cap_env("WCG_LOOKUP_LDS_MIN", &v)) lds_min = v;
+    const bool lds = nq >= lds_min;
+    if (mode == LK_COUNT && lds) k_lookup<LK_COUNT, true><<<(unsigned)grid, LK_NT, 0, c->stream>>>(c->sorted, c->sorted_n, c->arena, k, o, nq, out);
+    else if (mode == LK_COUNT) k_lookup<LK_COUNT, false><<<(unsigned)grid, LK_NT, 0, c->stream>>>(c->sorted, c->sorted_n, c->arena, k, o, nq, out);
+    else k_lookup<LK_INDEX, false><<<(unsigned)grid, LK_NT, 0, c->stream>>>(c->sorted, c->sorted_n, c->arena, k, o, nq, out);
+    HIPCHK(c, hipGetLastError());
+    return WCG_OK;
+}
+
+int wcg_lookup_device(wcg_ctx* c, const void* dev_keys, const void* dev_key_off, uint64_t nq, void* dev_counts) {
+    if (!c) return WCG_EINVAL;
+    RC(query_state(c, "wcg_lookup"));
+    if (nq == 0) return WCG_OK;
+    if (!dev_key_off || !dev_counts) { c->err = "wcg_lookup: null offsets or counts"; return WCG_EINVAL; }
+    if (c->sorted_n == 0) {                          // an empty job: no key occurs
+        HIPCHK(c, hipMemsetAsync(dev_counts, 0, nq * sizeof(u64), c->stream));
+        return WCG_OK;
+    }
+    return lookup_launch(c, LK_COUNT, dev_keys, dev_key_off, nq, static_cast<u64*>(dev_counts));
+}
+
+int wcg_lookup(wcg_ctx* c, const uint8_t* keys, const uint64_t* key_off, uint64_t nq, uint64_t* counts) {
+    if (!c) return WCG_EINVAL;
+    RC(query_state(c, "wcg_lookup"));
+    if (nq == 0) return WCG_OK;
+    if (!key_off || !counts || key_off[0] != 0) { c->err = "wcg_lookup: null offsets or counts, or key_off[0] != 0"; return WCG_EINVAL; }
+    for (u64 i = 0; i < nq; i++)
+        if (key_off[i + 1] < key_off[i]) { c->err = "wcg_lookup: key_off decreases"; return WCG_EINVAL; }
+    const u64 nb = key_off[nq];
+    if (nb && !keys) { c->err = "wcg_lookup: null keys"; return WCG_EINVAL; }
+    RC(ensure(c, &c->q_keys, &c->q_keys_cap, nb + 1));
+    RC(ensure(c, &c->q_off, &c->q_off_cap, nq + 1));
+    RC(ensure(c, &c->q_cnt, &c->q_cnt_cap, nq));
+    if (nb) HIPCHK(c, hipMemcpyAsync(c->q_keys, keys, nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->q_off, key_off, (nq + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    RC(wcg_lookup_device(c, c->q_keys, c->q_off, nq, c->q_cnt));
+    HIPCHK(c, hipMemcpyAsync(counts, c->q_cnt, nq * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return WCG_OK;
+}
+
+// the lines of the sorted records [a, b) in c->d_range (cached until the next job)
+static int range_format(wcg_ctx* c, u64 a, u64 b) {
+    if (c->range_ok && c->range_a == a && c->range_b == b) return WCG_OK;
+    c->range_ok = false;
+    u64 lines = 0, bytes = 0;
+    if (a < b) {
+        const u64 grid = std::min<u64>(cdiv(b - a, RS_NT), RS_MAXG);
+        RC(ensure(c, &c->rs_part, &c->rs_part_cap, 2 * (u64)RS_MAXG + 2));
+        u64* const tot = c->rs_part + 2 * RS_MAXG;
+        k_range_size<<<(unsigned)grid, RS_NT, 0, c->stream>>>(c->sorted, a, b, c->rs_part);
+        k_range_total<<<1, RS_NT, 0, c->stream>>>(c->rs_part, (u32)grid, tot);
+        HIPCHK(c, hipGetLastError());
+        // {lines, bytes}: the formatter's buffer is sized exactly, as wcg_top's is (a key may be
+        // megabytes long, and the merged file's bound would double the output memory)
+        u64* const h = c->h_scalar + 20;
+        HIPCHK(c, hipMemcpyAsync(h, tot, 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        lines = h[0]; bytes = h[1];
+        u64 got = 0;
+        RC(format(c, c->sorted + a, b - a, c->arena, FMT_MERGED, 1, 0, bytes, &c->d_range, &c->range_cap, &got));
+        if (got != bytes) { c->err = "wcg_range: formatted size mismatch"; return WCG_EHIP; }
+    }
+    c->range_a = a; c->range_b = b;
+    c->range_lines = lines; c->range_bytes = bytes;
+    c->range_ok = true;
+    return WCG_OK;
+}
+
+int wcg_range(wcg_ctx* c, const uint8_t* lo, uint64_t lo_len, const uint8_t* hi, uint64_t hi_len, uint8_t* host_out,
+              uint64_t cap, uint64_t* nlines, uint64_t* nbytes) {
+    if (!c) return WCG_EINVAL;
+    RC(query_state(c, "wcg_range"));
+    // the bounds' lower bounds among the sorted records: lo == NULL is index 0, hi == NULL the end
+    u64 ab[2] = {0, c->sorted_n};
+    const u64 nq = (lo ? 1 : 0) + (hi ? 1 : 0);
+    if (nq && c->sorted_n) {
+        u64 off[3] = {0, lo ? lo_len : 0, (lo ? lo_len : 0) + (hi ? hi_len : 0)};
+        if (!lo) off[1] = off[2];
+        RC(ensure(c, &c->q_keys, &c->q_keys_cap, off[nq] + 1));
+        RC(ensure(c, &c->q_off, &c->q_off_cap, 3));
+        RC(ensure(c, &c->q_cnt, &c->q_cnt_cap, 2));
+        if (lo && lo_len) HIPCHK(c, hipMemcpyAsync(c->q_keys, lo, lo_len, hipMemcpyHostToDevice, c->stream));
+        if (hi && hi_len) HIPCHK(c, hipMemcpyAsync(c->q_keys + (lo ? lo_len : 0), hi, hi_len, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->q_off, off, (nq + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+        RC(lookup_launch(c, LK_INDEX, c->q_keys, c->q_off, nq, c->q_cnt));
+        u64* const h = c->h_scalar + 22;
+        HIPCHK(c, hipMemcpyAsync(h, c->q_cnt, nq * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (lo) ab[0] = h[0];
+        if (hi) ab[1] = h[nq - 1];
+    }
+    if (ab[0] > ab[1]) ab[0] = ab[1];                // lo > hi: no lines, one cache entry
+    RC(range_format(c, ab[0], ab[1]));
+    if (nlines) *nlines = c->range_lines;
+    if (nbytes) *nbytes = c->range_bytes;
+    if (host_out) {
+        if (cap < c->range_bytes) { c->err = "wcg_range: buffer too small"; return WCG_EINVAL; }
+        if (c->range_bytes) {
+            HIPCHK(c, hipMemcpyAsync(host_out, c->d_range, c->range_bytes, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    return WCG_OK;
+}
+
 int wcg_export_count(wcg_ctx* c, uint32_t nreduce, uint32_t nranks, uint64_t* counts) {
     if (!c || !counts || nreduce == 0 || nranks == 0 || nranks > EX_MAX_RANKS) return WCG_EINVAL;
     RC(resolve(c));
@@ -2094,7 +2234,7 @@ int wcg_import(wcg_ctx* c, const void* dev_records, uint64_t nrecords) {
     c->imported = true;
     c->compacted = c->reduced = c->merged = false;
     c->exp_ready = false;
-    c->part_R = 0; c->top_n = 0;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false;
     return WCG_OK;          // a full table is reported by the next wcg_reduce / wcg_export_count
 }
 
@@ -2108,7 +2248,7 @@ int wcg_merge_runs(wcg_ctx* c, const void* dev_text, const uint64_t* run_bytes, 
     for (u32 r = 0; r < nruns; r++) total += run_bytes[r];
     c->compacted = false;
     c->exp_ready = false;
-    c->part_R = 0; c->top_n = 0;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false;
     c->reduced = false;
     if (total == 0) {
         c->nrec = 0; c->nkeys = 0; c->out_len = 0; c->reduced = true; c->merged = true;

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # WCG_LIB: an alternative build of the same library (measurement variants only)
@@ -28,6 +28,7 @@ EXPORTED = [
     "wcg_comm_id", "wcg_comm_init", "wcg_exchange", "wcg_gather_merge", "wcg_exchange_plan",
     "wcg_gather_plan", "wcg_exchange_local", "wcg_gather_merge_local", "wcg_reduce_path",
     "wcg_reduce_async", "wcg_reduce_wait", "wcg_ingest_stats", "wcg_top", "wcg_map_size_check",
+    "wcg_lookup", "wcg_lookup_device", "wcg_range",
 ]
 COMM_ID_BYTES = 128
 TOP_MAX = 1024                            # WCG_TOP_MAX
@@ -92,6 +93,9 @@ def load() -> ctypes.CDLL:
         "wcg_ingest_stats": (I, [P, ctypes.POINTER(ctypes.c_double), I]),
         "wcg_top": (I, [P, U32, P, U64, PU64, PU64]),
         "wcg_map_size_check": (I, [U64]),
+        "wcg_lookup": (I, [P, ctypes.c_char_p, PU64, U64, PU64]),
+        "wcg_lookup_device": (I, [P, P, P, U64, P]),
+        "wcg_range": (I, [P, ctypes.c_char_p, U64, ctypes.c_char_p, U64, P, U64, PU64, PU64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -282,6 +286,50 @@ class Engine:
         nl2, nb2 = ctypes.c_uint64(), ctypes.c_uint64()
         self._chk(self._lib.wcg_top(self._ctx, n, buf, nb, ctypes.byref(nl2), ctypes.byref(nb2)))
         return buf.raw[:nb2.value]
+
+    def lookup(self, words: Sequence[bytes]) -> List[int]:
+        """The count of every word in the last reduce, 0 for a word that does not occur, in the
+        order asked (wcg_lookup: binary searches on the device; only the counts come back).  Any
+        bytes may be asked for."""
+        nq = len(words)
+        if nq == 0:
+            self._chk(self._lib.wcg_lookup(self._ctx, None, None, 0, None))
+            return []
+        off = (ctypes.c_uint64 * (nq + 1))()
+        total = 0
+        for i, w in enumerate(words):
+            total += len(w)
+            off[i + 1] = total
+        counts = (ctypes.c_uint64 * nq)()
+        self._chk(self._lib.wcg_lookup(self._ctx, b"".join(words), off, nq, counts))
+        return list(counts)
+
+    def lookup_device(self, keys_ptr: int, off_ptr: int, nq: int, counts_ptr: int) -> None:
+        """wcg_lookup_device: key bytes, nq + 1 u64 offsets and nq u64 counts in device memory;
+        asynchronous on the engine's stream (sync() or a stream wait before the counts are read)."""
+        self._chk(self._lib.wcg_lookup_device(self._ctx, ctypes.c_void_p(keys_ptr), ctypes.c_void_p(off_ptr), nq,
+                                              ctypes.c_void_p(counts_ptr)))
+
+    def range_size(self, lo: Optional[bytes] = None, hi: Optional[bytes] = None) -> Tuple[int, int]:
+        """wcg_range with host_out == NULL: (lines, bytes) of range(lo, hi); the lines stay on the device."""
+        nl, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._lib.wcg_range(self._ctx, lo, len(lo) if lo is not None else 0, hi,
+                                      len(hi) if hi is not None else 0, None, 0, ctypes.byref(nl), ctypes.byref(nb)))
+        return nl.value, nb.value
+
+    def range(self, lo: Optional[bytes] = None, hi: Optional[bytes] = None) -> bytes:
+        """The merged file's lines with lo <= key < hi (bytewise; None: unbounded on that side),
+        found and formatted on the device: what range_of_merged(result(), lo, hi) computes."""
+        _, nb = self.range_size(lo, hi)
+        buf = ctypes.create_string_buffer(max(nb, 1))
+        nl2, nb2 = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._lib.wcg_range(self._ctx, lo, len(lo) if lo is not None else 0, hi,
+                                      len(hi) if hi is not None else 0, buf, nb, ctypes.byref(nl2), ctypes.byref(nb2)))
+        return buf.raw[:nb2.value]
+
+    def prefix(self, p: bytes) -> bytes:
+        """The merged file's lines whose key starts with p: range(p, prefix_succ(p))."""
+        return self.range(p, prefix_succ(p))
 
     def export(self, nreduce: int, nranks: int) -> Tuple[int, List[int]]:
         """Bucket the local aggregate by owner rank; returns (device ptr, units per rank)."""
@@ -499,6 +547,37 @@ def top_merge(parts: List[bytes], n: int) -> bytes:
     items = [it for p in parts for it in _count_lines(p)]
     items.sort()
     return _lines_of(items[-n:])
+
+
+def _key_lines(merged: bytes) -> List[Tuple[bytes, bytes]]:
+    """(key, line) of every "key: count\\n" line, in the file's order"""
+    out = []
+    for line in merged.split(b"\n"):
+        if line:
+            out.append((line.rpartition(b": ")[0], line + b"\n"))
+    return out
+
+
+def lookup_in_merged(merged: bytes, words: Sequence[bytes]) -> List[int]:
+    """What Engine.lookup(words) computes, stated on the host: each word's count in the merged
+    file ("key: count\\n" lines), 0 for a word that has no line; counts are Python integers."""
+    counts = {k: c for c, k in _count_lines(merged)}
+    return [counts.get(bytes(w), 0) for w in words]
+
+
+def range_of_merged(merged: bytes, lo: Optional[bytes] = None, hi: Optional[bytes] = None) -> bytes:
+    """What Engine.range(lo, hi) computes, stated on the host: the merged file's lines whose key k
+    has lo <= k < hi as byte strings (Python's bytes order: bytewise, a prefix first), in the
+    file's order; None leaves that side open."""
+    return b"".join(line for k, line in _key_lines(merged)
+                    if (lo is None or lo <= k) and (hi is None or k < hi))
+
+
+def prefix_succ(p: bytes) -> Optional[bytes]:
+    """The least byte string above every string that starts with p: p without its trailing 0xFF
+    bytes and with its last byte incremented; None (no upper bound) when p is empty or all 0xFF."""
+    q = bytes(p).rstrip(b"\xff")
+    return q[:-1] + bytes([q[-1] + 1]) if q else None
 
 
 def version() -> str:

@@ -6,6 +6,9 @@
   python -m wcg.wc top <file> <N>                    the N most frequent words to stdout: what
                                                      `sort -n -k2 mrtmp.<file> | tail -<N>` prints
                                                      (test-wc.sh:2-3), selected on the GPU
+  python -m wcg.wc count <file> <word>...            "<word>: <count>" per argument, in argument
+                                                     order, zeros included, looked up on the GPU
+  python -m wcg.wc prefix <file> <P>                 the merged file's lines whose key starts with P
 
 nMap = 5, nReduce = 3 and nRPC = 100 are wc.go's constants (wc.go:49,51,56).  Environment knobs a
 harness may set without changing that interface: WCG_DEVICE (HIP device of this process, default
@@ -105,7 +108,42 @@ def top(path: str, n: int = 10) -> bytes:
     raise AssertionError("unreachable")
 
 
+def _reduced(path: str, query):
+    """query(engine) after Split + DoMap + reduce of a file, as top() runs them"""
+    from ._lib import WcgError, WCG_EFULL
+    size = os.path.getsize(path)
+    for dense in (False, True):
+        with engine_for(size, dense) as e:
+            try:
+                e.map_file(path)
+                e.reduce()
+                return query(e)
+            except WcgError as err:
+                if err.status != WCG_EFULL or dense:
+                    raise
+    raise AssertionError("unreachable")
+
+
+def count(path: str, words) -> list:
+    """How often each of `words` (bytes) occurs in a file, 0 included, in the order asked: the
+    counts its merged file gives them, looked up on the GPU (Engine.lookup); writes no mrtmp.* files."""
+    words = list(words)
+    return _reduced(path, lambda e: e.lookup(words))
+
+
+def prefix(path: str, p: bytes) -> bytes:
+    """The merged file's lines of a file whose key starts with p, selected on the GPU
+    (Engine.prefix); writes no mrtmp.* files."""
+    return _reduced(path, lambda e: e.prefix(p))
+
+
 def main(argv) -> int:
+    if len(argv) >= 4 and argv[1] == "count":
+        words = [os.fsencode(w) for w in argv[3:]]
+        out = b"".join(w + b": %d\n" % n for w, n in zip(words, count(argv[2], words)))
+        sys.stdout.buffer.write(out)
+        sys.stdout.buffer.flush()
+        return 0
     if len(argv) != 4:                    # wc.go:45-46: a note, exit status 0
         print(f"{argv[0]}: see usage comments in file")
         return 0
@@ -117,6 +155,9 @@ def main(argv) -> int:
             mr.MapReduce(NMAP, NREDUCE, argv[2], argv[3], workdir).wait()
     elif argv[1] == "top":
         sys.stdout.buffer.write(top(argv[2], int(argv[3])))
+        sys.stdout.buffer.flush()
+    elif argv[1] == "prefix":
+        sys.stdout.buffer.write(prefix(argv[2], os.fsencode(argv[3])))
         sys.stdout.buffer.flush()
     else:
         nrpc = int(os.environ.get("WCG_NRPC", str(NRPC)))
