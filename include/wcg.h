@@ -111,7 +111,8 @@ WCG_API int wcg_reduce(wcg_ctx *ctx, uint64_t *nkeys, uint64_t *nbytes);
  * wcg_reduce_wait returns what wcg_reduce would have (sizes, or the job's error); every call that
  * reads the job's results (wcg_result_*, wcg_partition*, wcg_export*, wcg_stats, wcg_timings,
  * wcg_sync, the collectives) waits for it first.  A job not waited for before the next wcg_reset
- * / wcg_map* / wcg_import is dropped, its results and its error status with it.  Jobs that take
+ * / wcg_map / wcg_map_device / wcg_map_file / wcg_import is dropped, its results and its error
+ * status with it (wcg_map_json aggregates nothing and leaves the job alone).  Jobs that take
  * the multi-launch reduce (the first job of a context, large or two-pass jobs) are reduced
  * synchronously here as by wcg_reduce. */
 WCG_API int wcg_reduce_async(wcg_ctx *ctx);
@@ -196,7 +197,13 @@ WCG_API int wcg_range(wcg_ctx *ctx, const uint8_t *lo, uint64_t lo_len, const ui
  * token, in input order, the line {"Key":"tok","Value":"1"}\n in file ihash(tok) % nreduce - the
  * bytes the reference's json.Encoder writes to mrtmp.<f>-<m>-<r>, so an unmodified CPU DoReduce
  * can consume GPU map output.  Files back to back in partition order; part_bytes[nreduce] gets
- * each size; host_out == NULL queries the sizes only.  Independent of the aggregation tables. */
+ * each size; host_out == NULL queries the sizes only; cap < the files' total: WCG_EINVAL.
+ * nreduce <= 1024, as for wcg_partition_all: 0 or more is WCG_EINVAL, checked before anything is
+ * allocated, copied or launched (the split is walked once per 128 partitions).  Independent of the
+ * aggregation tables: the call neither reads nor changes the keys mapped so far, the last
+ * wcg_reduce()'s result or what wcg_partition*, wcg_top, wcg_lookup and wcg_range cache of it, and
+ * it is not one of the wcg_map* calls that drop a pending wcg_reduce_async job (it only waits for
+ * the stream the job runs on; wcg_reduce_wait then returns the job's sizes as usual). */
 WCG_API int wcg_map_json(wcg_ctx *ctx, const uint8_t *host_bytes, uint64_t n, uint32_t nreduce,
                          uint8_t *host_out, uint64_t cap, uint64_t *part_bytes);
 

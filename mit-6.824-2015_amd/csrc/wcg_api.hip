@@ -2314,6 +2314,9 @@ int wcg_merge_runs(wcg_ctx* c, const void* dev_text, const uint64_t* run_bytes, 
 int wcg_map_json(wcg_ctx* c, const uint8_t* host_bytes, uint64_t n, uint32_t nreduce, uint8_t* host_out, uint64_t cap,
                  uint64_t* part_bytes) {
     if (!c || nreduce == 0 || (n && !host_bytes)) return WCG_EINVAL;
+    // the kernels walk the split once per JS_PG partitions and the host reads back nreduce * W
+    // offsets: the partition calls' limit, checked before anything is allocated, copied or launched
+    if (nreduce > PT_MAXR) { c->err = "wcg_map_json: nreduce above " + std::to_string(PT_MAXR); return WCG_EINVAL; }
     int rc = set_dev(c);
     if (rc) return rc;
     c->jparts.assign(nreduce, 0);
