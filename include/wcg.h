@@ -23,6 +23,8 @@
  *   wcg_map_file ~ Split + DoMap x nMap from the input file (mapreduce.go:141-179, 193-231)
  *   wcg_merge_runs ~ Merge of the owners' sorted DoReduce outputs  (mapreduce.go:284-321)
  *   wcg_map_json ~ DoMap's per-occurrence JSON intermediates       (mapreduce.go:214-230)
+ *   wcg_index_merged / wcg_load_merged ~ the merged file mrtmp.<f> made searchable (test-wc.sh:2-3
+ *                  asks its question of that file)
  *
  * Conventions:
  *   - Every entry point returns int status (WCG_OK = 0); the host turns non-zero into a fatal
@@ -159,7 +161,8 @@ WCG_API int wcg_partition_all(wcg_ctx *ctx, uint32_t nreduce, uint8_t *host_out,
  * n > WCG_TOP_MAX: WCG_EINVAL (take the merged file).  Requires a prior wcg_reduce() (a pending
  * wcg_reduce_async job is waited for): WCG_ESTATE before one, after wcg_free of its result, and
  * after wcg_merge_runs / wcg_gather_merge* on the context that holds the merged file (its records
- * are lines without counts; wcg.top_merge in Python combines the ranks' tops instead).  The result
+ * are lines without counts) until wcg_index_merged has made query records of them; without that
+ * call, wcg.top_merge in Python combines the ranks' tops on the host.  The result
  * calls, wcg_partition*, wcg_export*, wcg_stats and wcg_timings in between do not disturb it (they
  * leave the sorted records alone; should an export ever have to regrow the record buffers,
  * wcg_top reports WCG_ESTATE rather than read freed records). */
@@ -174,7 +177,7 @@ WCG_API int wcg_top(wcg_ctx *ctx, uint32_t n, uint8_t *host_out, uint64_t cap, u
  * are allowed: an empty key, a key holding a NUL or 0xFF byte or a non-letter simply does not
  * occur.  nq == 0 is WCG_OK and touches nothing.  State rules as wcg_top's: WCG_ESTATE before a
  * wcg_reduce() (a pending wcg_reduce_async job is waited for), after wcg_free of its result and
- * after wcg_merge_runs / wcg_gather_merge*; the result calls, wcg_partition*, wcg_export*, wcg_top,
+ * after wcg_merge_runs / wcg_gather_merge* (until wcg_index_merged); the result calls, wcg_partition*, wcg_export*, wcg_top,
  * wcg_stats and wcg_timings in between do not disturb it.  After wcg_exchange every key has one
  * owner, so a word's count over all ranks is the sum of the ranks' lookups. */
 WCG_API int wcg_lookup(wcg_ctx *ctx, const uint8_t *keys, const uint64_t *key_off, uint64_t nq,
@@ -292,6 +295,40 @@ WCG_API int wcg_gather_merge_local(wcg_ctx **ctxs, uint32_t world, uint32_t root
  * (wcg_result_device / wcg_result_copy).  Synchronous. */
 WCG_API int wcg_merge_runs(wcg_ctx *ctx, const void *dev_text, const uint64_t *run_bytes, uint32_t nruns,
                            uint64_t *nkeys, uint64_t *nbytes);
+
+/* Query a merged file.  wcg_index_merged builds, on the device, the records wcg_top, wcg_lookup,
+ * wcg_lookup_device and wcg_range search, for the merged file this context holds: valid after
+ * wcg_merge_runs, wcg_gather_merge* (on the root) and wcg_load_merged*.  Every line is checked on
+ * the way (wcg.check_merged states the rules in Python); per line, in this order:
+ *   count  the line is key, ": ", a canonical decimal in 1 .. 2^64-1 (first digit 1-9, at most 20
+ *          digits), '\n'; the key is not empty and ends at the line's first ':'
+ *   zero   the count is not "0"
+ *   nul    the key holds no zero byte
+ *   order  the key sorts strictly after the previous line's (bytewise, a prefix first): equal
+ *          adjacent keys are rejected (the runs of a merge have disjoint keys by contract)
+ * A file that breaks a rule: WCG_EINVAL, and wcg_last_error() reads
+ * "wcg_index_merged: line <N>: <rule> (...)" for the first such line (N counts from 0); the
+ * wcg_result_* calls still return the merged bytes and the queries stay WCG_ESTATE.  Afterwards
+ * the queries work exactly as after wcg_reduce, with the same caches; *nlines = the file's lines.
+ * Synchronous.  A second call, or a call on a context whose result came from wcg_reduce (*nlines =
+ * its key count), does nothing and returns WCG_OK; before any result: WCG_ESTATE.  An empty merged
+ * file indexes to zero records (lookups give zeros, top and range no lines).  The merged file is
+ * the records' key storage: wcg_free of the result buffer drops the index (queries are WCG_ESTATE
+ * again), as wcg_reset, wcg_map*, wcg_import, a new merge and wcg_reduce drop any result.
+ * wcg_partition*, wcg_export*, wcg_exchange* and wcg_gather_merge* on a merged context stay
+ * WCG_ESTATE, indexed or not.  Without the call nothing changes: wcg_merge_runs launches what it
+ * always did. */
+WCG_API int wcg_index_merged(wcg_ctx *ctx, uint64_t *nlines);
+
+/* One sorted "key: count\n" file (yesterday's mrtmp.<file>, or one the CPU reference wrote) into
+ * this context as its merged result, indexed: wcg_merge_runs with one run (except that the file is
+ * checked, not trusted: no line is moved), then wcg_index_merged.  The host form copies the file
+ * to the device through the context's pinned staging buffers.  n > 0 with a last byte other than
+ * '\n' is WCG_EINVAL ("newline" in wcg_last_error), checked before anything is copied or launched
+ * (the host form: before the device is touched; the device form reads that one byte first).  Like
+ * wcg_merge_runs they drop a pending wcg_reduce_async job and are synchronous. */
+WCG_API int wcg_load_merged(wcg_ctx *ctx, const uint8_t *host_bytes, uint64_t n, uint64_t *nlines);
+WCG_API int wcg_load_merged_device(wcg_ctx *ctx, const void *dev_bytes, uint64_t n, uint64_t *nlines);
 
 /* Per-phase device time of the last pipeline run, in milliseconds, measured with HIP events
  * on the context's stream: ms[0] map kernel (tokenize + LDS aggregation, summed over the

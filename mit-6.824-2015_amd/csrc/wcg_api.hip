@@ -31,6 +31,7 @@
 #include "wcg_reduce.h"
 #include "wcg_top.h"
 #include "wcg_query.h"
+#include "wcg_index.h"
 #include "wcg_fused.h"
 #include "wcg_ingest.h"
 
@@ -131,6 +132,8 @@ struct wcg_ctx {
     u64* d_b0 = nullptr; u64 b0_cap = 0;
     bool merged = false;                      // the result is a merge of runs (wcg_merge_runs): the
                                               // sorted records are line records, not keys
+    bool indexed = false;                     // ... until wcg_index_merged made query records of them
+                                              // (meaningful while merged; their arena is d_out)
     // RCCL shuffle (wcg_comm_init / wcg_exchange / wcg_gather_merge)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -217,6 +220,10 @@ u64 next_pow2(u64 x) {
 }
 
 u64 cdiv(u64 a, u64 b) { return (a + b - 1) / b; }
+
+// the arena of the sorted records (where c->sorted's long keys point): the long-key arena after a
+// reduce, the merged file itself after wcg_index_merged
+const uint8_t* sorted_arena(const wcg_ctx* c) { return c->merged && c->indexed ? c->d_out : c->arena; }
 
 int set_dev(wcg_ctx* c) {
     hipError_t e = hipSetDevice(c->device);
@@ -1886,6 +1893,7 @@ int wcg_free(wcg_ctx* c, const void* dev_ptr) {
         HIPCHK(c, hipFree(c->d_out));
         c->d_out = nullptr; c->out_cap = 0; c->out_len = 0;
         c->reduced = false;
+        c->indexed = false;                          // the merged file was the index's arena
         return WCG_OK;
     }
     if (dev_ptr == c->exp_buf) {
@@ -2007,7 +2015,7 @@ static int top_select(wcg_ctx* c, u32 n) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const u64 lines = h[0], bytes = h[1];
     u64 got = 0;
-    RC(format(c, c->top_rec, q, c->arena, FMT_MERGED, 1, 0, bytes, &c->d_top, &c->top_cap, &got));
+    RC(format(c, c->top_rec, q, sorted_arena(c), FMT_MERGED, 1, 0, bytes, &c->d_top, &c->top_cap, &got));
     if (got != bytes) { c->err = "wcg_top: formatted size mismatch"; return WCG_EHIP; }
     c->top_lines = lines;
     c->top_bytes = bytes;
@@ -2019,7 +2027,7 @@ int wcg_top(wcg_ctx* c, uint32_t n, uint8_t* host_out, uint64_t cap, uint64_t* n
     if (!c) return WCG_EINVAL;
     RC(resolve(c));
     if (!c->reduced) { c->err = "wcg_top before wcg_reduce"; return WCG_ESTATE; }
-    if (c->merged) { c->err = "wcg_top after wcg_merge_runs (a merged file's records carry no counts)"; return WCG_ESTATE; }
+    if (c->merged && !c->indexed) { c->err = "wcg_top after wcg_merge_runs (a merged file's records carry no counts; wcg_index_merged makes them)"; return WCG_ESTATE; }
     if (!c->sorted_live) { c->err = "wcg_top: the sorted records were released (record buffers regrown); wcg_reduce again"; return WCG_ESTATE; }
     if (n > WCG_TOP_MAX) { c->err = "wcg_top: n above WCG_TOP_MAX (1024)"; return WCG_EINVAL; }
     int rc = set_dev(c);
@@ -2042,7 +2050,7 @@ static int query_state(wcg_ctx* c, const char* who) {
     RC(resolve(c));
     const char* why = nullptr;
     if (!c->reduced) why = " before wcg_reduce";
-    else if (c->merged) why = " after wcg_merge_runs (a merged file's records carry no counts)";
+    else if (c->merged && !c->indexed) why = " after wcg_merge_runs (a merged file's records carry no counts; wcg_index_merged makes them)";
     else if (!c->sorted_live) why = ": the sorted records were released (record buffers regrown); wcg_reduce again";
     if (why) { c->err = std::string(who) + why; return WCG_ESTATE; }
     return set_dev(c);
@@ -2063,9 +2071,9 @@ static int lookup_launch(wcg_ctx* c, int mode, const void* keys, const void* off
     u64 lds_min = LK_LDS_MIN;
     if (cap_env("WCG_LOOKUP_LDS_MIN", &v)) lds_min = v;
     const bool lds = nq >= lds_min;
-    if (mode == LK_COUNT && lds) k_lookup<LK_COUNT, true><<<(unsigned)grid, LK_NT, 0, c->stream>>>(c->sorted, c->sorted_n, c->arena, k, o, nq, out);
-    else if (mode == LK_COUNT) k_lookup<LK_COUNT, false><<<(unsigned)grid, LK_NT, 0, c->stream>>>(c->sorted, c->sorted_n, c->arena, k, o, nq, out);
-    else k_lookup<LK_INDEX, false><<<(unsigned)grid, LK_NT, 0, c->stream>>>(c->sorted, c->sorted_n, c->arena, k, o, nq, out);
+    if (mode == LK_COUNT && lds) k_lookup<LK_COUNT, true><<<(unsigned)grid, LK_NT, 0, c->stream>>>(c->sorted, c->sorted_n, sorted_arena(c), k, o, nq, out);
+    else if (mode == LK_COUNT) k_lookup<LK_COUNT, false><<<(unsigned)grid, LK_NT, 0, c->stream>>>(c->sorted, c->sorted_n, sorted_arena(c), k, o, nq, out);
+    else k_lookup<LK_INDEX, false><<<(unsigned)grid, LK_NT, 0, c->stream>>>(c->sorted, c->sorted_n, sorted_arena(c), k, o, nq, out);
     HIPCHK(c, hipGetLastError());
     return WCG_OK;
 }
@@ -2121,7 +2129,7 @@ static int range_format(wcg_ctx* c, u64 a, u64 b) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         lines = h[0]; bytes = h[1];
         u64 got = 0;
-        RC(format(c, c->sorted + a, b - a, c->arena, FMT_MERGED, 1, 0, bytes, &c->d_range, &c->range_cap, &got));
+        RC(format(c, c->sorted + a, b - a, sorted_arena(c), FMT_MERGED, 1, 0, bytes, &c->d_range, &c->range_cap, &got));
         if (got != bytes) { c->err = "wcg_range: formatted size mismatch"; return WCG_EHIP; }
     }
     c->range_a = a; c->range_b = b;
@@ -2238,10 +2246,14 @@ int wcg_import(wcg_ctx* c, const void* dev_records, uint64_t nrecords) {
     return WCG_OK;          // a full table is reported by the next wcg_reduce / wcg_export_count
 }
 
-int wcg_merge_runs(wcg_ctx* c, const void* dev_text, const uint64_t* run_bytes, uint32_t nruns, uint64_t* nkeys,
-                   uint64_t* nbytes) {
+// wcg_merge_runs.  file = true (wcg_load_merged*): the one run is a file to be checked, not trusted:
+// its lines keep the file's order (no tie groups are sorted, so wcg_index_merged names the line that
+// is out of order) and a line k_line_recs could not read is left to wcg_index_merged's count rule
+static int merge_runs(wcg_ctx* c, const void* dev_text, const uint64_t* run_bytes, uint32_t nruns, uint64_t* nkeys,
+                      uint64_t* nbytes, bool file) {
     if (!c || (nruns && !run_bytes)) return WCG_EINVAL;
     c->pending = false;
+    c->indexed = false;
     int rc = set_dev(c);
     if (rc) return rc;
     u64 total = 0;
@@ -2298,17 +2310,120 @@ int wcg_merge_runs(wcg_ctx* c, const void* dev_text, const uint64_t* run_bytes, 
     c->sorted = src;
     c->nrec = L;
     c->nkeys = L;
-    RC(fix_ties(c, src, L, text, dst));
+    if (!file) RC(fix_ties(c, src, L, text, dst));
     RC(dbg(c, "merge_runs: ties"));
     RC(format(c, src, L, text, FMT_COPY, 1, 0, total, &c->d_out, &c->out_cap, &c->out_len));
     HIPCHK(c, hipMemcpyAsync(c->h_st, c->st, sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_st->bad_input) { c->err = "wcg_merge_runs: a line is not \"key: count\""; return WCG_EINVAL; }
+    if (c->h_st->bad_input && !file) { c->err = "wcg_merge_runs: a line is not \"key: count\""; return WCG_EINVAL; }
+    if (c->h_st->bad_input) HIPCHK(c, hipMemsetAsync(&c->st->bad_input, 0, sizeof(u32), c->stream));   // (file: the index reports the line)
     c->reduced = true;
     c->merged = true;
     if (nkeys) *nkeys = L;
     if (nbytes) *nbytes = c->out_len;
     return WCG_OK;
+}
+
+int wcg_merge_runs(wcg_ctx* c, const void* dev_text, const uint64_t* run_bytes, uint32_t nruns, uint64_t* nkeys,
+                   uint64_t* nbytes) {
+    return merge_runs(c, dev_text, run_bytes, nruns, nkeys, nbytes, false);
+}
+
+// the merged file's line records -> query records in the other record buffer (wcg_index.h); the
+// line records stay where they are until every rule held, so a failed call can be repeated
+int wcg_index_merged(wcg_ctx* c, uint64_t* nlines) {
+    if (!c) return WCG_EINVAL;
+    RC(resolve(c));
+    if (!c->reduced) { c->err = "wcg_index_merged before a result (wcg_reduce, wcg_merge_runs, wcg_gather_merge*, wcg_load_merged*)"; return WCG_ESTATE; }
+    if (!c->merged || c->indexed) {                  // wcg_reduce's records, or indexed already
+        if (nlines) *nlines = c->nkeys;
+        return WCG_OK;
+    }
+    int rc = set_dev(c);
+    if (rc) return rc;
+    const u64 L = c->nrec;
+    if (L) {
+        const u64 nt = cdiv(L, FM_TILE);
+        // tests, measurements: WCG_INDEX_STAGE may only lower the bytes of a tile that go through
+        // LDS (0: every tile is read in place); read on every call like WCG_TOP_GRID
+        u64 stage = FM_STAGE, v;
+        if (cap_env("WCG_INDEX_STAGE", &v)) stage = std::min(stage, v);
+        Rec* const dst = c->sorted == c->recA ? c->recB : c->recA;
+        u64* const err = c->d_scalar + ST_IX_ERR;
+        RC(ensure(c, &c->lens, &c->lens_cap, nt + 1));
+        HIPCHK(c, hipMemsetAsync(err, 0xFF, IX_KINDS * sizeof(u64), c->stream));
+        k_ix_sum<<<(unsigned)nt, FM_NT, 0, c->stream>>>(c->sorted, L, c->lens);
+        k_scan_u64<<<1, 1024, 0, c->stream>>>(c->lens, nt, c->d_scalar);
+        k_ix_write<<<(unsigned)nt, FM_NT, 0, c->stream>>>(c->sorted, L, c->d_out, c->out_len, c->lens, dst, err, (u32)stage);
+        HIPCHK(c, hipGetLastError());
+        u64* const h = c->h_scalar + ST_IX_ERR;
+        HIPCHK(c, hipMemcpyAsync(h, err, IX_KINDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h + IX_KINDS, c->d_scalar, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        static const char* const kind[IX_KINDS] = {
+            "count (the line is not key, \": \", a canonical decimal in 1 .. 2^64-1, newline)",
+            "zero (a count of 0)", "nul (a zero byte in the key)",
+            "order (the key does not sort strictly after the previous line's)"};
+        int worst = -1;
+        for (int k = 0; k < IX_KINDS; k++)
+            if (h[k] != IX_NONE && (worst < 0 || h[k] < h[worst])) worst = k;
+        if (worst >= 0) {
+            c->err = "wcg_index_merged: line " + std::to_string(h[worst]) + ": " + kind[worst];
+            return WCG_EINVAL;
+        }
+        if (h[IX_KINDS] != c->out_len) { c->err = "wcg_index_merged: the line records do not cover the merged file"; return WCG_EHIP; }
+        c->sorted = dst;
+    }
+    c->sorted_n = L;
+    c->sorted_live = true;
+    c->indexed = true;
+    c->top_n = 0; c->range_ok = false;
+    if (nlines) *nlines = L;
+    return WCG_OK;
+}
+
+int wcg_load_merged_device(wcg_ctx* c, const void* dev_bytes, uint64_t n, uint64_t* nlines) {
+    if (!c || (n && !dev_bytes)) return WCG_EINVAL;
+    c->pending = false;
+    int rc = set_dev(c);
+    if (rc) return rc;
+    if (n) {                                         // the last byte, before anything is launched
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        uint8_t last = 0;
+        HIPCHK(c, hipMemcpy(&last, static_cast<const uint8_t*>(dev_bytes) + n - 1, 1, hipMemcpyDeviceToHost));
+        if (last != '\n') { c->err = "wcg_load_merged_device: newline (the file does not end with one)"; return WCG_EINVAL; }
+    }
+    const uint64_t run = n;
+    RC(merge_runs(c, dev_bytes, &run, 1, nullptr, nullptr, true));
+    return wcg_index_merged(c, nlines);
+}
+
+int wcg_load_merged(wcg_ctx* c, const uint8_t* host_bytes, uint64_t n, uint64_t* nlines) {
+    if (!c || (n && !host_bytes)) return WCG_EINVAL;
+    if (n && host_bytes[n - 1] != '\n') { c->err = "wcg_load_merged: newline (the file does not end with one)"; return WCG_EINVAL; }
+    c->pending = false;
+    int rc = set_dev(c);
+    if (rc) return rc;
+    if (n) {
+        // through the ingest's pinned staging buffers, alternating: the host copy of one chunk
+        // overlaps the transfer of the previous one.  The file lands where a gather's runs do.
+        RC(ingest_init(c));
+        RC(ensure(c, &c->grecv, &c->grecv_cap, n + 64));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        int slot = 0;
+        bool used[INGEST_SLOTS] = {};
+        for (u64 off = 0; off < n; off += c->chunk, slot = (slot + 1) % INGEST_SLOTS) {
+            const u64 len = std::min<u64>(c->chunk, n - off);
+            if (used[slot]) HIPCHK(c, hipEventSynchronize(c->ev_copied[slot]));
+            memcpy(c->hb[slot], host_bytes + off, len);
+            HIPCHK(c, hipMemcpyAsync(c->grecv + off, c->hb[slot], len, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipEventRecord(c->ev_copied[slot], c->stream));
+            used[slot] = true;
+        }
+    }
+    const uint64_t run = n;
+    RC(merge_runs(c, c->grecv, &run, 1, nullptr, nullptr, true));
+    return wcg_index_merged(c, nlines);
 }
 
 int wcg_map_json(wcg_ctx* c, const uint8_t* host_bytes, uint64_t n, uint32_t nreduce, uint8_t* host_out, uint64_t cap,

@@ -78,6 +78,7 @@ constexpr u64 ST_GLIST = 24;         // scalar slot: two-pass contexts' global-t
 constexpr u64 GLIST_CAP = 1ull << 20;   // claims listed (more: compaction and reset scan it all)
 constexpr u64 ST_LLIST = 25;         // scalar slot: large contexts' long-key-table claim list, or 0
 constexpr u64 LLIST_CAP = 1ull << 22;   // (C4 1 GiB: 1.6M long keys in a 16M-slot, 512 MiB table)
+constexpr u64 ST_IX_ERR = 32;        // scalar slots [32, 36): wcg_index_merged's lowest offending line per rule
 struct DevState {
     u64 tokens;          // tokens seen by map kernels
     u64 lds_hits;        // tokens aggregated in LDS

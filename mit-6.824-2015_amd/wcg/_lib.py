@@ -28,7 +28,8 @@ EXPORTED = [
     "wcg_comm_id", "wcg_comm_init", "wcg_exchange", "wcg_gather_merge", "wcg_exchange_plan",
     "wcg_gather_plan", "wcg_exchange_local", "wcg_gather_merge_local", "wcg_reduce_path",
     "wcg_reduce_async", "wcg_reduce_wait", "wcg_ingest_stats", "wcg_top", "wcg_map_size_check",
-    "wcg_lookup", "wcg_lookup_device", "wcg_range",
+    "wcg_lookup", "wcg_lookup_device", "wcg_range", "wcg_index_merged", "wcg_load_merged",
+    "wcg_load_merged_device",
 ]
 COMM_ID_BYTES = 128
 TOP_MAX = 1024                            # WCG_TOP_MAX
@@ -96,6 +97,9 @@ def load() -> ctypes.CDLL:
         "wcg_lookup": (I, [P, ctypes.c_char_p, PU64, U64, PU64]),
         "wcg_lookup_device": (I, [P, P, P, U64, P]),
         "wcg_range": (I, [P, ctypes.c_char_p, U64, ctypes.c_char_p, U64, P, U64, PU64, PU64]),
+        "wcg_index_merged": (I, [P, PU64]),
+        "wcg_load_merged": (I, [P, ctypes.c_char_p, U64, PU64]),
+        "wcg_load_merged_device": (I, [P, P, U64, PU64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -360,6 +364,27 @@ class Engine:
                                            ctypes.byref(nk), ctypes.byref(nb)))
         return nk.value, nb.value
 
+    def index_merged(self) -> int:
+        """wcg_index_merged: make the merged file this engine holds (after merge_runs, gather_merge
+        on the root, load_merged) queryable by top / lookup / range / prefix; returns its lines.
+        A file that breaks a rule of check_merged raises WcgError(WCG_EINVAL) naming line and rule."""
+        nl = ctypes.c_uint64()
+        self._chk(self._lib.wcg_index_merged(self._ctx, ctypes.byref(nl)))
+        return nl.value
+
+    def load_merged(self, data: bytes) -> int:
+        """wcg_load_merged: one sorted "key: count\n" file (an mrtmp.<file> that already exists)
+        becomes this engine's merged result, checked and indexed; returns its lines."""
+        nl = ctypes.c_uint64()
+        self._chk(self._lib.wcg_load_merged(self._ctx, data, len(data), ctypes.byref(nl)))
+        return nl.value
+
+    def load_merged_device(self, dev_ptr: int, n: int) -> int:
+        """wcg_load_merged_device: the same for n bytes in device memory (synchronous)."""
+        nl = ctypes.c_uint64()
+        self._chk(self._lib.wcg_load_merged_device(self._ctx, ctypes.c_void_p(dev_ptr), n, ctypes.byref(nl)))
+        return nl.value
+
     # -- the shuffle and the final Merge over RCCL, inside the library
     @staticmethod
     def comm_id() -> bytes:
@@ -571,6 +596,55 @@ def range_of_merged(merged: bytes, lo: Optional[bytes] = None, hi: Optional[byte
     file's order; None leaves that side open."""
     return b"".join(line for k, line in _key_lines(merged)
                     if (lo is None or lo <= k) and (hi is None or k < hi))
+
+
+KEY_BYTES_MAX = (1 << 23) - 1             # LONG_LEN_MAX: the longest key a record describes
+MERGED_KINDS = ("count", "zero", "nul", "order", "newline")
+
+
+def check_merged(merged: bytes) -> Optional[Tuple[int, str]]:
+    """The rules Engine.index_merged / load_merged hold a merged file to, stated on the host: None
+    for a valid file, else (index of the first bad line, rule), the rule being the word
+    wcg_last_error uses.  A line's key ends at its first ':' (a line without one is all key).
+    Per line, in this order:
+      "count"  the line is key, ": ", a canonical decimal in 1 .. 2^64-1 (first digit 1-9, at most
+               20 digits), newline, and the key has 1 .. KEY_BYTES_MAX bytes
+      "zero"   the count is not "0"
+      "nul"    the key holds no zero byte
+      "order"  the key sorts strictly after the previous line's (Python's bytes order)
+    and, for the file, "newline": a last line without its newline (load_merged looks at this
+    first, so it is reported whatever the lines before hold)."""
+    merged = bytes(merged)
+    if merged and not merged.endswith(b"\n"):
+        return merged.count(b"\n"), "newline"
+    prev = None
+    for i, line in enumerate(merged.split(b"\n")[:-1]):
+        line += b"\n"
+        klen = line.find(b":")
+        if klen < 0:
+            klen = len(line)
+        key = line[:klen]
+        body = line[:-1]
+        nd = 0
+        while nd < 21 and nd < len(body) and 0x30 <= body[len(body) - 1 - nd] <= 0x39:
+            nd += 1
+        digits = body[len(body) - nd:]
+        bad = None
+        if nd == 0 or nd > 20 or klen == 0 or klen > KEY_BYTES_MAX or len(line) != klen + 3 + nd or line[klen:klen + 2] != b": ":
+            bad = "count"
+        elif digits[:1] == b"0":
+            bad = "zero" if nd == 1 else "count"
+        elif int(digits) > 0xFFFFFFFFFFFFFFFF:
+            bad = "count"
+        elif b"\0" in key:
+            bad = "nul"
+        if bad is None and prev is not None and not prev < key:
+            bad = "order"
+        # a zero byte in the key, or a key out of order, of a line whose count is bad: "count" stands
+        if bad is not None:
+            return i, bad
+        prev = key
+    return None
 
 
 def prefix_succ(p: bytes) -> Optional[bytes]:

@@ -137,16 +137,20 @@ def shuffle_reduce(engine, nreduce: int, group=None) -> int:
     return nkeys
 
 
-def gather_merge(engine, root: int = 0, group=None, fetch: bool = True) -> Optional[bytes]:
+def gather_merge(engine, root: int = 0, group=None, fetch: bool = True, index: bool = False) -> Optional[bytes]:
     """Merge (mapreduce.go:284-321) across ranks, after shuffle_reduce: every owner sends its
     sorted run (its formatted "key: count\n" output; the owners' key sets are disjoint) to
     `root`, which merges the runs on its GPU (wcg_merge_runs: ceil(log2 world) merge passes, no
     re-sort).  Returns the merged file bytes on root (fetch=False: leaves them in the root
-    engine's device buffer and returns b""), None elsewhere."""
+    engine's device buffer and returns b""), None elsewhere.  index=True: the root then indexes the
+    merged file (wcg_index_merged), so that top / lookup / range / prefix of the root engine answer
+    for the whole job; the other ranks' engines are not needed for that any more."""
     if getattr(engine, "in_library", False):         # wcg_gather_merge: RCCL inside the library
         engine.e.gather_merge(root)
         if dist.get_rank(group) != root:
             return None
+        if index:
+            engine.index_merged()
         return engine.result() if fetch else b""
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
@@ -157,6 +161,8 @@ def gather_merge(engine, root: int = 0, group=None, fetch: bool = True) -> Optio
     if rank != root:
         return None
     engine.merge_runs_tensor(recv, run_bytes)
+    if index:
+        engine.index_merged()
     return engine.result() if fetch else b""
 
 
@@ -229,3 +235,14 @@ class TorchEngine:
             t = t.to("cuda")
         self._before_engine()
         return self.e.merge_runs(t.data_ptr(), run_bytes)     # synchronous
+
+    def index_merged(self) -> int:
+        return self.e.index_merged()                          # synchronous, on the engine's stream
+
+    def load_merged_tensor(self, t: torch.Tensor) -> int:
+        """Engine.load_merged_device of a uint8 tensor holding one sorted "key: count\\n" file,
+        ordered against torch's stream as merge_runs_tensor is."""
+        if not t.is_cuda:
+            t = t.to("cuda")
+        self._before_engine()
+        return self.e.load_merged_device(t.data_ptr(), t.numel())   # synchronous

@@ -9,6 +9,10 @@
   python -m wcg.wc count <file> <word>...            "<word>: <count>" per argument, in argument
                                                      order, zeros included, looked up on the GPU
   python -m wcg.wc prefix <file> <P>                 the merged file's lines whose key starts with P
+  python -m wcg.wc top-merged <mrtmp> <N>            the same three questions asked of a merged file
+  python -m wcg.wc count-merged <mrtmp> <word>...    that already exists (mrtmp.<file>, ours or the
+  python -m wcg.wc prefix-merged <mrtmp> <P>         CPU reference's): checked, loaded and searched
+                                                     on the GPU, no input file and no re-run needed
 
 nMap = 5, nReduce = 3 and nRPC = 100 are wc.go's constants (wc.go:49,51,56).  Environment knobs a
 harness may set without changing that interface: WCG_DEVICE (HIP device of this process, default
@@ -137,7 +141,40 @@ def prefix(path: str, p: bytes) -> bytes:
     return _reduced(path, lambda e: e.prefix(p))
 
 
+def _loaded(path: str, query):
+    """query(engine) after Engine.load_merged of a merged file.  The engine is sized from the file's
+    line count (its keys), not from an input size; the aggregation tables stay unused."""
+    from ._lib import Engine
+    with open(path, "rb") as f:
+        data = f.read()
+    with Engine(device=_device(), max_input_bytes=0, max_keys=max(1 << 16, data.count(b"\n"))) as e:
+        e.load_merged(data)
+        return query(e)
+
+
+def top_merged(path: str, n: int = 10) -> bytes:
+    """top() asked of a merged file: `sort -n -k2 <path> | tail -n <n>`, selected on the GPU."""
+    return _loaded(path, lambda e: e.top(n))
+
+
+def count_merged(path: str, words) -> list:
+    """count() asked of a merged file: each word's count in it, 0 included, in the order asked."""
+    words = list(words)
+    return _loaded(path, lambda e: e.lookup(words))
+
+
+def prefix_merged(path: str, p: bytes) -> bytes:
+    """prefix() asked of a merged file: its lines whose key starts with p."""
+    return _loaded(path, lambda e: e.prefix(p))
+
+
 def main(argv) -> int:
+    if len(argv) >= 4 and argv[1] == "count-merged":
+        words = [os.fsencode(w) for w in argv[3:]]
+        out = b"".join(w + b": %d\n" % n for w, n in zip(words, count_merged(argv[2], words)))
+        sys.stdout.buffer.write(out)
+        sys.stdout.buffer.flush()
+        return 0
     if len(argv) >= 4 and argv[1] == "count":
         words = [os.fsencode(w) for w in argv[3:]]
         out = b"".join(w + b": %d\n" % n for w, n in zip(words, count(argv[2], words)))
@@ -155,6 +192,12 @@ def main(argv) -> int:
             mr.MapReduce(NMAP, NREDUCE, argv[2], argv[3], workdir).wait()
     elif argv[1] == "top":
         sys.stdout.buffer.write(top(argv[2], int(argv[3])))
+        sys.stdout.buffer.flush()
+    elif argv[1] == "top-merged":
+        sys.stdout.buffer.write(top_merged(argv[2], int(argv[3])))
+        sys.stdout.buffer.flush()
+    elif argv[1] == "prefix-merged":
+        sys.stdout.buffer.write(prefix_merged(argv[2], os.fsencode(argv[3])))
         sys.stdout.buffer.flush()
     elif argv[1] == "prefix":
         sys.stdout.buffer.write(prefix(argv[2], os.fsencode(argv[3])))
