@@ -364,6 +364,16 @@ WCG_API int wcg_ingest_stats(wcg_ctx *ctx, double *out, int n);
  * a context whose previous job had at most 2^17 keys), 0 for the multi-launch path. */
 WCG_API int wcg_reduce_path(const wcg_ctx *ctx, int *path);
 
+/* Diagnostics: the seed of the map kernel's LDS key tables.  A context that has reduced a one-pass
+ * job keeps that job's most frequent inline keys (<= 15 bytes) as a placed image, and its later
+ * one-pass map calls start their LDS tables from it instead of empty: fewer tokens miss the
+ * tables.  The seed is a hint like the record-count hint: it survives wcg_reset, and no result
+ * depends on it.  A seeded job whose share of tokens counted in LDS falls below that of the
+ * (unseeded) job the seed came from drops it; the next job runs unseeded and builds a new one.
+ * WCG_SEED=0 in the environment switches seeding off.  stats3 = {the context holds a seed, seeds
+ * built since wcg_open, the last finished job's map calls all ran seeded}. */
+WCG_API int wcg_seed_stats(wcg_ctx *ctx, uint64_t *stats3);
+
 /* FNV-1a 32 (= ihash, mapreduce.go:185-189), host side, for partition arithmetic. */
 WCG_API uint32_t wcg_ihash(const uint8_t *key, uint64_t len);
 

@@ -33,6 +33,7 @@
 #include "wcg_query.h"
 #include "wcg_index.h"
 #include "wcg_fused.h"
+#include "wcg_seed.h"
 #include "wcg_ingest.h"
 
 using namespace wcg;
@@ -193,6 +194,22 @@ struct wcg_ctx {
     bool pending = false;                     // wcg_reduce_async queued a job not yet read back
     uint16_t* flist = nullptr; u64 flist_cap = 0;   // r05: k_agg's one-pass flush lists
     u64* h_st_dev = nullptr;                  // h_st's device address (the fused launch writes it)
+    // The seed of k_map's LDS key tables (wcg_seed.h): the image and the builder's scratch in one
+    // allocation.  A hint like nrec_hint: it survives wcg_reset and no result depends on it.
+    //   seed_ok     the image is built (by kernels queued on the stream: valid for any later launch)
+    //   seed_rate   lds_hits / tokens of the job it was built from (< 0: that job was never read back)
+    //   job_*       since wcg_reset: map calls launched with / without the seed; this job's reduce built it
+    u64* seed = nullptr;
+    bool seed_ok = false;
+    double seed_rate = -1.0;
+    bool job_seeded = false, job_unseeded = false, job_built = false;
+    bool last_seeded = false;                 // the last finished job ran seeded map calls only
+    u64 seed_builds = 0;                      // images built since wcg_open (wcg_seed_stats)
+    // diagnostic buffers (WCG_AGG_CLOCK, WCG_FUSED_CLOCK, WCG_STAMPS builds): per context, as every
+    // context writes them on its own stream
+    u64* d_clk = nullptr;
+    u64* d_fclk = nullptr;
+    u64* d_stamps = nullptr;
     std::string err;
 };
 
@@ -420,6 +437,71 @@ int compact(wcg_ctx* c, bool defer = false) {
 // launch reports).  WCG_FUSED=0 keeps the multi-launch path (A/B, tests).
 u64 merged_bound(wcg_ctx* c, u64 n, bool json);
 
+// ---- the seed of k_map's LDS key tables (wcg_seed.h).  Host policy:
+//   * one-pass map calls of a context whose seed is built launch k_map<MAP_SEEDED, true>;
+//   * a reduce of a one-pass job builds the image behind itself when the context has none (three
+//     small launches on the context's stream, no read-back), so a steady stream of jobs pays nothing;
+//   * when a job's counters are on the host (they come with the job's sizes), a seeded job's
+//     lds_hits / tokens is compared with the rate of the unseeded job the seed was built from: below
+//     it, the seed is stale (another corpus) and is dropped; the next job maps unseeded, as every
+//     job did before seeds, and its reduce builds the new one.  A corpus change costs one slow job,
+//     never a wrong one.  The builder job's counters are also kept beside the image, for a seed
+//     whose builder job was never read back (a wcg_reduce_async job dropped by the next map call).
+// WCG_SEED=0 switches all of it off (A/B runs, tests); read on every call like WCG_FUSED_TARGET.
+bool seed_on(const wcg_ctx* c) {
+    const char* e = getenv("WCG_SEED");
+    return !(e && atoi(e) == 0) && !c->two_pass_used && !c->imported;
+}
+
+// build the image from sorted records [0, n), n = min(*dev_n, ncap) when dev_n is given (the count
+// is still on the device); nhint sizes the grids only
+int seed_build(wcg_ctx* c, const Rec* rec, u64 ncap, const u64* dev_n, u64 nhint) {
+    if (!c->seed) HIPCHK(c, hipMalloc(&c->seed, SEED_ALLOC_BYTES));
+    SeedScratch* sc = reinterpret_cast<SeedScratch*>(c->seed + SEED_IMG_WORDS);
+    HIPCHK(c, hipMemsetAsync(sc, 0, SEED_ZERO_BYTES, c->stream));
+    const int grid = grid_for(std::max<u64>(nhint, 1), SEED_NT, 2 * c->ncu);
+    k_seed_hist<<<grid, SEED_NT, 0, c->stream>>>(rec, ncap, dev_n, sc);
+    k_seed_pick<<<grid, SEED_NT, 0, c->stream>>>(rec, ncap, dev_n, sc);
+    k_seed_place<<<1, SEED_PLACE_NT, 0, c->stream>>>(sc, c->seed, c->st);
+    HIPCHK(c, hipGetLastError());
+    c->seed_ok = true;
+    c->seed_builds++;
+    if (getenv("WCG_DEBUG")) fprintf(stderr, "wcg seed: build %llu\n", (unsigned long long)c->seed_builds);
+    return WCG_OK;
+}
+
+// should this job's reduce build the image?  (a job of map calls, none of them seeded)
+bool seed_wanted(const wcg_ctx* c) { return seed_on(c) && !c->seed_ok && c->job_unseeded; }
+
+// the job's counters are in h_st and its sorted records in c->sorted[0, c->nrec)
+int seed_job_done(wcg_ctx* c) {
+    const bool built = c->job_built;
+    c->job_built = false;
+    c->last_seeded = c->job_seeded && !c->job_unseeded;
+    if (!c->seed_ok) return WCG_OK;
+    const u64 tokens = c->h_st->tokens;
+    const double rate = tokens ? (double)c->h_st->lds_hits / (double)tokens : -1.0;
+    if (built) { c->seed_rate = rate; return WCG_OK; }      // (seed_wanted: an unseeded job)
+    if (!c->last_seeded || rate < 0) return WCG_OK;
+    if (c->seed_rate < 0) {
+        // the builder job was never read back: its counters, kept beside the image (the stream is
+        // idle here, and this happens once per seed)
+        u64 job[2] = {0, 0};
+        const SeedScratch* sc = reinterpret_cast<const SeedScratch*>(c->seed + SEED_IMG_WORDS);
+        HIPCHK(c, hipMemcpyAsync(job, sc->job, sizeof job, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->seed_rate = job[0] ? (double)job[1] / (double)job[0] : 0.0;
+    }
+    // stale: the seed is dropped, the next job maps unseeded and its reduce builds a new one, so
+    // seed_rate is always an unseeded job's rate (a stale job's own rate as the new reference would
+    // hide the next corpus change whose stale rate happens to lie above it)
+    if (rate < c->seed_rate) {
+        c->seed_ok = false;
+        if (getenv("WCG_DEBUG")) fprintf(stderr, "wcg seed: stale (%.4f < %.4f), dropped\n", rate, c->seed_rate);
+    }
+    return WCG_OK;
+}
+
 bool fused_eligible(wcg_ctx* c) {
     static const char* env = getenv("WCG_FUSED");
     static const bool exact_env = getenv("WCG_EXACT_REDUCE") != nullptr || getenv("WCG_SORT_TARGET") != nullptr;
@@ -469,11 +551,11 @@ int reduce_fused(wcg_ctx* c) {
     a.nitems0 = (u32)cdiv(total, (u64)CP_NT * CP_IPT);
     if (c->timing_all) { c->phase_ev[2] = take_event(c); HIPCHK(c, hipEventRecord(c->phase_ev[2], c->stream)); }
     static const bool fclock = getenv("WCG_FUSED_CLOCK") != nullptr;   // diagnostics: phase clocks
-    static u64* d_fclk = nullptr;
+    u64*& d_fclk = c->d_fclk;
     const unsigned fgrid = (unsigned)(2 * c->ncu);
     a.clk = nullptr;
     if (fclock) {
-        if (!d_fclk) HIPCHK(c, hipMalloc(&d_fclk, ((u64)fgrid * FR_CLK + 8ull * FR_NPH * FR_CLK_ITEMS + 8ull * FR_NPH) * sizeof(u64)));
+        if (!d_fclk) HIPCHK(c, hipMalloc(&d_fclk,((u64)fgrid * FR_CLK + 8ull * FR_NPH * FR_CLK_ITEMS + 8ull * FR_NPH) * sizeof(u64)));
         HIPCHK(c, hipMemsetAsync(d_fclk, 0, ((u64)fgrid * FR_CLK + 8ull * FR_NPH * FR_CLK_ITEMS + 8ull * FR_NPH) * sizeof(u64), c->stream));
         a.clk = d_fclk;
     }
@@ -569,6 +651,11 @@ int reduce_fused(wcg_ctx* c) {
         }
     }
     if (c->timing_all) { c->phase_ev[3] = take_event(c); HIPCHK(c, hipEventRecord(c->phase_ev[3], c->stream)); }
+    // no seed yet: built behind the launch from its sorted records (their count is st->nrec)
+    if (seed_wanted(c)) {
+        RC(seed_build(c, c->recB, c->rec_cap, &c->st->nrec, c->nrec_hint));
+        c->job_built = true;
+    }
     // the job's one host round trip: counters, errors and the formatted size, written into the
     // pinned host block by the launch's last workgroup (waited for by reduce_fused_finish: at once
     // in wcg_reduce, later after wcg_reduce_async)
@@ -587,13 +674,14 @@ int reduce_fused_finish(wcg_ctx* c) {
     c->out_len = *c->h_scalar;
     if (c->h_st->bad_input || c->h_st->overflow || c->h_st->spin_fail) {
         c->nrec = 0; c->out_len = 0; c->reduced = false;
+        if (c->job_built) { c->job_built = false; c->seed_ok = false; }   // built from a failed job's records
         RC(check_status(c));                      // the error message (nothing was compacted)
     }
     c->nrec_hint = c->nrec;
     c->long_hint = c->h_st->long_tokens;
     c->sorted_live = true;
     c->sorted_n = c->nrec;
-    return WCG_OK;
+    return seed_job_done(c);
 }
 
 // a wcg_reduce_async job's results, before anything that reads them
@@ -1164,7 +1252,8 @@ int wcg_close(wcg_ctx* c) {
                     c->llog, c->llog_len, c->smp, c->bid, c->spx, c->irec, c->lent, c->lpcur, c->spill, c->spill_len, c->pool2, c->rlen2, c->remit, c->ovf, c->hist, c->spart, c->ikey, c->iidx, c->groups,
                     c->pid, c->d_partb, c->nlpos, c->d_rb, c->d_b0, c->d_jin, c->d_jout, c->jhist, c->dbig,
                     c->d_xrow, c->xrecv, c->grecv, c->glist, c->llist, c->fr_buf, c->flist,
-                    c->top_cand, c->top_rec, c->d_top, c->q_keys, c->q_off, c->q_cnt, c->rs_part, c->d_range};
+                    c->top_cand, c->top_rec, c->d_top, c->q_keys, c->q_off, c->q_cnt, c->rs_part, c->d_range,
+                    c->seed, c->d_clk, c->d_fclk, c->d_stamps};
     if (c->comm) (void)ncclCommDestroy(c->comm);
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (c->h_x) (void)hipHostFree(c->h_x);
@@ -1373,6 +1462,7 @@ extern "C" {
 int wcg_reset(wcg_ctx* c) {
     if (!c) return WCG_EINVAL;
     c->pending = false;                 // a wcg_reduce_async job not waited for is dropped
+    c->job_seeded = c->job_unseeded = c->job_built = false;
     int rc = set_dev(c);
     if (rc) return rc;
     if (c->timing_mode >= 2 && c->ev_used >= EV_FOLD) {   // recycle the events of earlier jobs
@@ -1514,8 +1604,13 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
     a.region_len = c->region_len;
     a.wg_stats = c->wg_stats;
     a.stamps = nullptr;
+    // the seed of the LDS key tables (one-pass calls of a context that has built one)
+    static const int ablate = getenv("WCG_MAP_ABLATE") ? atoi(getenv("WCG_MAP_ABLATE")) : 0;
+    const bool seeded = split && ablate == 0 && c->seed_ok && seed_on(c);
+    a.seed = seeded ? c->seed : nullptr;
+    (seeded ? c->job_seeded : c->job_unseeded) = true;
 #if WCG_STAMPS
-    static u64* d_stamps = nullptr;
+    u64*& d_stamps = c->d_stamps;
     if (!d_stamps) HIPCHK(c, hipMalloc(&d_stamps, MAP_NSTAMP * sizeof(u64)));
     HIPCHK(c, hipMemsetAsync(d_stamps, 0, MAP_NSTAMP * sizeof(u64), c->stream));
     a.stamps = d_stamps;
@@ -1524,7 +1619,6 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
     // as separate stream markers cost a ~5 us bubble each between the kernels around them)
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     if (c->timing) { e0 = take_event(c); e1 = take_event(c); }
-    static const int ablate = getenv("WCG_MAP_ABLATE") ? atoi(getenv("WCG_MAP_ABLATE")) : 0;
     auto launch = [&](auto kern) {
         if (e0) hipExtLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(MAP_NT), 0, c->stream, e0, e1, 0u, a);
         else kern<<<(unsigned)grid, MAP_NT, 0, c->stream>>>(a);
@@ -1537,7 +1631,10 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
         case 5: split ? launch(k_map<5, true>) : launch(k_map<5, false>); break;
         case 6: split ? launch(k_map<6, true>) : launch(k_map<6, false>); break;
         case 7: split ? launch(k_map<7, true>) : launch(k_map<7, false>); break;
-        default: split ? launch(k_map<0, true>) : launch(k_map<0, false>); break;
+        default:
+            if (seeded) launch(k_map<MAP_SEEDED, true>);
+            else split ? launch(k_map<0, true>) : launch(k_map<0, false>);
+            break;
     }
     HIPCHK(c, hipGetLastError());
 #if WCG_STAMPS
@@ -1638,7 +1735,7 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
         g.flist = c->flist;
     }
     static const bool agg_clock = getenv("WCG_AGG_CLOCK") != nullptr;
-    static u64* d_clk = nullptr;
+    u64*& d_clk = c->d_clk;
     if (agg_clock && !two_pass) {          // diagnostics: per-workgroup time against its units
         if (!d_clk) HIPCHK(c, hipMalloc(&d_clk, 2 * 65536 * sizeof(u64)));
         g.clk = nb1 <= 65536 ? d_clk : nullptr;
@@ -1820,6 +1917,11 @@ int wcg_reduce(wcg_ctx* c, uint64_t* nkeys, uint64_t* nbytes) {
     }
     c->nrec_hint = c->nrec;
     if (c->h_st) c->long_hint = c->h_st->long_tokens;     // (a hint: read back with the sizes)
+    if (c->nrec && seed_wanted(c)) {               // no seed yet: built from this job's sorted records
+        RC(seed_build(c, c->sorted, c->nrec, nullptr, c->nrec));
+        c->job_built = true;
+    }
+    RC(seed_job_done(c));
     if (c->timing_all) {
         c->phase_ev[4] = take_event(c);
         HIPCHK(c, hipEventRecord(c->phase_ev[4], c->stream));
@@ -2898,6 +3000,15 @@ int wcg_timings(wcg_ctx* c, double* ms, int n, uint64_t* map_launches) {
 int wcg_reduce_path(const wcg_ctx* c, int* path) {
     if (!c || !path) return WCG_EINVAL;
     *path = c->fused_last ? 1 : 0;
+    return WCG_OK;
+}
+
+int wcg_seed_stats(wcg_ctx* c, uint64_t* s3) {   // 3 values (include/wcg.h)
+    if (!c || !s3) return WCG_EINVAL;
+    RC(resolve(c));
+    s3[0] = c->seed_ok ? 1 : 0;
+    s3[1] = c->seed_builds;
+    s3[2] = c->last_seeded ? 1 : 0;
     return WCG_OK;
 }
 

@@ -197,6 +197,21 @@ struct MapTable {
         if (seen) for (int i = tid; i < (int)(ADMIT_BITS / 32); i += nt) seen[i] = 0;
         if (tid == 0) *zero = 0;
     }
+    // the same, with the key words copied from a seed image (wcg_seed.h: sk0[NS] | mk0[NM] | mk1[NM],
+    // 16 bytes per load) instead of zeroed; counts, filter and the zero word as in init()
+    __device__ __forceinline__ void init_seeded(const u64* img, int tid, int nt) {
+        static_assert(NS % 2 == 0 && NM % 2 == 0, "16-byte copies");
+        const uint4* s = reinterpret_cast<const uint4*>(img);
+        for (int i = tid; i < NS / 2; i += nt) reinterpret_cast<uint4*>(sk0)[i] = s[i];
+        for (int i = tid; i < NM / 2; i += nt) {
+            reinterpret_cast<uint4*>(mk0)[i] = s[NS / 2 + i];
+            reinterpret_cast<uint4*>(mk1)[i] = s[NS / 2 + NM / 2 + i];
+        }
+        for (int i = tid; i < NS; i += nt) scnt[i] = 0;
+        for (int i = tid; i < NM; i += nt) mcnt[i] = 0;
+        if (seen) for (int i = tid; i < (int)(ADMIT_BITS / 32); i += nt) seen[i] = 0;
+        if (tid == 0) *zero = 0;
+    }
     // Admission on second sight: a key takes a free slot only if its filter bit was already set
     // (it missed once before); its first occurrence goes to the miss log like any miss.  The
     // table then fills with keys that recur, close to the most frequent ones, instead of with the

@@ -120,6 +120,7 @@ struct MapArgs {
     u32* llog_len;                 // records written per region
     Rec* emit;     u64 emit_cap;    // two-pass jobs: the record log (k_long_hash's inline runs)
     u64* stamps;                    // WCG_STAMPS builds: MAP_NSTAMP sums over all waves
+    const u64* seed;                // k_map<MAP_SEEDED, *>: the seed image (wcg_seed.h)
 };
 constexpr u64 LLOG_OFF_MASK = (1ull << 40) - 1;   // record = input offset | len << 40 (len 0: walk)
 constexpr u32 LLOG_PER_STEP = 64;                 // long-token log records per step: a bound (a
@@ -937,6 +938,10 @@ __device__ __forceinline__ u32 wave_incl_scan(u32 x) {
 //   short-key iterations' decodes and probes (no table update, no miss, no unit store - and none
 //   counted in the step's stores; medium iterations in full); 6 = full but long tokens only
 //   counted, 7 = full but long tokens only measured and hashed
+//   MAP_SEEDED (8) is no ablation: the full kernel, exact, whose prologue copies the context's seed
+//   image (wcg_seed.h) into the LDS key tables instead of zeroing them.  An instance of its own,
+//   through the existing parameter, so that k_map<0, *> stay the code the ISA tests pin.
+constexpr int MAP_SEEDED = 8;
 // ---- r04: the letter mask of a wave's window with non-ASCII bytes, by a wave-wide list of the
 //      UTF-8 leads.  The lead-compacted form (utf8_mask_lds) decodes eight lead slots per lane,
 //      so a wave pays max-over-lanes (8 on C4: ~615 VALU per step, half of k_map's time there);
@@ -1137,7 +1142,8 @@ __global__ __launch_bounds__(MAP_NT, MAP_WGS * MAP_NT / 256) WCG_MAP_ATTR void k
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform (scalar)
     MapTable<MAP_NS, MAP_NM> tab{sk0, scnt, mk0, mk1, mcnt, &zero_w, WCG_ADMIT2 ? seen_w : nullptr};
-    tab.init(tid, MAP_NT);
+    if (ABL == MAP_SEEDED) tab.init_seeded(a.seed, tid, MAP_NT);
+    else tab.init(tid, MAP_NT);
     for (int i = tid; i < MAX_MISS_BUCKETS; i += MAP_NT) cursor[i] = 0;
     if (tid == 0) lcur = 0;
     lds_letters_init(lt_idx, lt_bits, tid, MAP_NT);

@@ -29,7 +29,7 @@ EXPORTED = [
     "wcg_gather_plan", "wcg_exchange_local", "wcg_gather_merge_local", "wcg_reduce_path",
     "wcg_reduce_async", "wcg_reduce_wait", "wcg_ingest_stats", "wcg_top", "wcg_map_size_check",
     "wcg_lookup", "wcg_lookup_device", "wcg_range", "wcg_index_merged", "wcg_load_merged",
-    "wcg_load_merged_device",
+    "wcg_load_merged_device", "wcg_seed_stats",
 ]
 COMM_ID_BYTES = 128
 TOP_MAX = 1024                            # WCG_TOP_MAX
@@ -100,8 +100,11 @@ def load() -> ctypes.CDLL:
         "wcg_index_merged": (I, [P, PU64]),
         "wcg_load_merged": (I, [P, ctypes.c_char_p, U64, PU64]),
         "wcg_load_merged_device": (I, [P, P, U64, PU64]),
+        "wcg_seed_stats": (I, [P, PU64]),
     }
     for name, (res, args) in sig.items():
+        if os.environ.get("WCG_LIB") and not hasattr(lib, name):
+            continue                          # a measurement variant built from an older tree
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -468,6 +471,13 @@ class Engine:
         v = (ctypes.c_double * len(self.INGEST_STATS))()
         self._chk(self._lib.wcg_ingest_stats(self._ctx, v, len(self.INGEST_STATS)))
         return dict(zip(self.INGEST_STATS, list(v)))
+
+    def seed_stats(self) -> dict:
+        """The seed of k_map's LDS key tables (wcg_seed_stats): whether the context holds one, how
+        many it has built, and whether the last finished job's map calls all ran seeded."""
+        s = (ctypes.c_uint64 * 3)()
+        self._chk(self._lib.wcg_seed_stats(self._ctx, s))
+        return {"valid": bool(s[0]), "builds": int(s[1]), "last_job_seeded": bool(s[2])}
 
     def stats(self) -> dict:
         s = (ctypes.c_uint64 * 9)()
