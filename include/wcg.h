@@ -25,6 +25,8 @@
  *   wcg_map_json ~ DoMap's per-occurrence JSON intermediates       (mapreduce.go:214-230)
  *   wcg_index_merged / wcg_load_merged ~ the merged file mrtmp.<f> made searchable (test-wc.sh:2-3
  *                  asks its question of that file)
+ *   wcg_import_json ~ DoReduce's and Merge's reading of the JSON files (mapreduce.go:242-263,
+ *                  289-303): mrtmp.<f>-<m>-<r> and mrtmp.<f>-res-<r> decoded on the device
  *
  * Conventions:
  *   - Every entry point returns int status (WCG_OK = 0); the host turns non-zero into a fatal
@@ -114,7 +116,8 @@ WCG_API int wcg_reduce(wcg_ctx *ctx, uint64_t *nkeys, uint64_t *nbytes);
  * reads the job's results (wcg_result_*, wcg_partition*, wcg_export*, wcg_stats, wcg_timings,
  * wcg_sync, the collectives) waits for it first.  A job not waited for before the next wcg_reset
  * / wcg_map / wcg_map_device / wcg_map_file / wcg_import is dropped, its results and its error
- * status with it (wcg_map_json aggregates nothing and leaves the job alone).  Jobs that take
+ * status with it (wcg_map_json aggregates nothing and leaves the job alone; wcg_import_json drops
+ * it when it accepts its file and leaves it alone when it refuses it).  Jobs that take
  * the multi-launch reduce (the first job of a context, large or two-pass jobs) are reduced
  * synchronously here as by wcg_reduce. */
 WCG_API int wcg_reduce_async(wcg_ctx *ctx);
@@ -329,6 +332,45 @@ WCG_API int wcg_index_merged(wcg_ctx *ctx, uint64_t *nlines);
  * wcg_merge_runs they drop a pending wcg_reduce_async job and are synchronous. */
 WCG_API int wcg_load_merged(wcg_ctx *ctx, const uint8_t *host_bytes, uint64_t n, uint64_t *nlines);
 WCG_API int wcg_load_merged_device(wcg_ctx *ctx, const void *dev_bytes, uint64_t n, uint64_t *nlines);
+
+/* The reference's JSON files into the aggregation tables, decoded on the device: lines
+ * {"Key":"<key>","Value":"<value>"}\n as Go's json.Encoder writes them for letter-only keys.
+ *   WCG_JSON_MAP  DoMap's intermediates mrtmp.<f>-<m>-<r> (mapreduce.go:214-230, what wcg_map_json
+ *                 writes): every line is one occurrence of its key, its value is "1"
+ *   WCG_JSON_RES  DoReduce's mrtmp.<f>-res-<r> (mapreduce.go:264-279, what wcg_partition* writes):
+ *                 the line's value is its key's count
+ * The file's keys are added to the context's tables as by wcg_map* / wcg_import: onto a live table
+ * or after wcg_reset, counts adding as unsigned 64-bit; a full table is reported by the next
+ * wcg_reduce / wcg_export_count.  *nlines = the lines imported.  Synchronous.  The host form copies
+ * the file to a library-owned device buffer through the context's pinned staging buffers (as
+ * wcg_load_merged) and then runs the device form's code.
+ *   Parity.  MAP mode over the -<m>-<r> files of every map job m, then wcg_reduce and
+ * wcg_partition(1, 0), gives the bytes DoReduce(r) writes (mapreduce.go:239-280).  RES mode over
+ * every -res-<r>, then wcg_reduce, gives Merge's file (mapreduce.go:284-321) when the files' keys
+ * are disjoint (a job's always are); a key present in several files adds, where Merge's map would
+ * keep the last.
+ *   n == 0: WCG_OK, nothing is touched.  A NULL pointer with n > 0, or another mode: WCG_EINVAL.
+ * n > 0 with a last byte other than '\n': WCG_EINVAL ("newline" in wcg_last_error), checked first
+ * (the host form: before the device is touched; the device form reads that one byte).
+ *   The file is checked whole before anything is aggregated.  Per line (B = the line without its
+ * '\n', L = its length), in this order:
+ *   frame  L >= 10, B starts with {"Key":" and ends with "}
+ *   value  V = the run of bytes other than '"' that ends at L-2, followed back for at most 21 bytes
+ *          and never into B[0..8): V is not empty and a '"' opens it within those bounds; MAP: V is
+ *          the single byte 1; RES: V is a canonical decimal in 1 .. 2^64-1 (first digit 1-9, at
+ *          most 20 digits, no wrap)
+ *   sep    the 11 bytes that end with V's opening quote are ","Value":" and begin at offset >= 8
+ *   key    K = B[8 .. L-2-len(V)-11) has 1 .. 2^23-1 bytes and Go's tokenizer returns exactly K for
+ *          K: every rune is valid UTF-8 and a unicode.IsLetter letter (so quotes, backslash
+ *          escapes, digits, NUL and invalid UTF-8 all break it; letter-only keys never need JSON
+ *          escaping, so the reference's decoder yields the same key bytes)
+ * A file that breaks a rule: WCG_EINVAL, wcg_last_error() reads "wcg_import_json: line <N>: <rule>"
+ * for the lowest offending line (N counts from 0) and the first rule it breaks; the context is
+ * exactly as it was (tables, the last result and its caches, a pending wcg_reduce_async job).  An
+ * accepted file drops results and pending jobs exactly as wcg_import does. */
+enum { WCG_JSON_MAP = 0, WCG_JSON_RES = 1 };
+WCG_API int wcg_import_json(wcg_ctx *ctx, const uint8_t *host_bytes, uint64_t n, int mode, uint64_t *nlines);
+WCG_API int wcg_import_json_device(wcg_ctx *ctx, const void *dev_bytes, uint64_t n, int mode, uint64_t *nlines);
 
 /* Per-phase device time of the last pipeline run, in milliseconds, measured with HIP events
  * on the context's stream: ms[0] map kernel (tokenize + LDS aggregation, summed over the

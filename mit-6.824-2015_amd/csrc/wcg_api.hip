@@ -32,6 +32,7 @@
 #include "wcg_top.h"
 #include "wcg_query.h"
 #include "wcg_index.h"
+#include "wcg_import_json.h"
 #include "wcg_fused.h"
 #include "wcg_seed.h"
 #include "wcg_ingest.h"
@@ -149,6 +150,12 @@ struct wcg_ctx {
     uint8_t* d_jout = nullptr; u64 jout_cap = 0;
     u64* jhist = nullptr; u64 jhist_cap = 0;
     std::vector<u64> jparts;
+    // the reference's JSON files read back (wcg_import_json, wcg_import_json.h): buffers of their own,
+    // so that a refused file leaves everything else of the context as it was
+    uint8_t* ij_in = nullptr; u64 ij_in_cap = 0;      // the host form's copy of the file
+    u64* ij_tiles = nullptr; u64 ij_tiles_cap = 0;    // per tile: lines, line start, output size; 8 control words
+    uint8_t* ij_keys = nullptr; u64 ij_keys_cap = 0;  // MAP: the "key\n" text
+    Rec* ij_units = nullptr; u64 ij_units_cap = 0;    // RES: the exchange units
     // miss log (k_map -> k_agg)
     u64* pool = nullptr; u64 pool_bytes = 0;
     u32* region_len = nullptr; u64 region_len_cap = 0;
@@ -1251,6 +1258,7 @@ int wcg_close(wcg_ctx* c) {
                     c->d_part, c->owner, c->d_per_rank, c->exp_buf, c->pool, c->region_len, c->wg_stats,
                     c->llog, c->llog_len, c->smp, c->bid, c->spx, c->irec, c->lent, c->lpcur, c->spill, c->spill_len, c->pool2, c->rlen2, c->remit, c->ovf, c->hist, c->spart, c->ikey, c->iidx, c->groups,
                     c->pid, c->d_partb, c->nlpos, c->d_rb, c->d_b0, c->d_jin, c->d_jout, c->jhist, c->dbig,
+                    c->ij_in, c->ij_tiles, c->ij_keys, c->ij_units,
                     c->d_xrow, c->xrecv, c->grecv, c->glist, c->llist, c->fr_buf, c->flist,
                     c->top_cand, c->top_rec, c->d_top, c->q_keys, c->q_off, c->q_cnt, c->rs_part, c->d_range,
                     c->seed, c->d_clk, c->d_fclk, c->d_stamps};
@@ -2526,6 +2534,100 @@ int wcg_load_merged(wcg_ctx* c, const uint8_t* host_bytes, uint64_t n, uint64_t*
     const uint64_t run = n;
     RC(merge_runs(c, c->grecv, &run, 1, nullptr, nullptr, true));
     return wcg_index_merged(c, nlines);
+}
+
+// wcg_import_json*: the file at dev_bytes (its last byte is '\n', n > 0).  Nothing of the context
+// but the ij_* buffers is touched until every line has passed (wcg_import_json.h).
+static int import_json(wcg_ctx* c, const uint8_t* text, u64 n, int mode, uint64_t* nlines) {
+    const u64 nt = cdiv(n, IJ_TILE);
+    if (nt > 0x7FFFFFFFull) { c->err = "wcg_import_json: more tiles than a grid holds"; return WCG_EINVAL; }
+    RC(ensure(c, &c->ij_tiles, &c->ij_tiles_cap, 3 * nt + 8));
+    u64 *const lines = c->ij_tiles, *const start = lines + nt, *const osz = start + nt, *const ctl = osz + nt;
+    HIPCHK(c, hipMemsetAsync(ctl, 0xFF, IJ_KINDS * sizeof(u64), c->stream));
+    k_ij_nl<<<(unsigned)nt, IJ_NT, 0, c->stream>>>(text, n, lines, start);
+    k_scan_u64<<<1, 1024, 0, c->stream>>>(lines, nt, ctl + 4);
+    k_ij_maxscan<<<1, 1024, 0, c->stream>>>(start, nt);
+    k_ij_check<<<(unsigned)nt, IJ_NT, 0, c->stream>>>(text, n, mode, lines, start, osz, ctl);
+    k_scan_u64<<<1, 1024, 0, c->stream>>>(osz, nt, ctl + 5);
+    HIPCHK(c, hipGetLastError());
+    u64 h[6];
+    HIPCHK(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    static const char* const kind[IJ_KINDS] = {"frame", "value", "sep", "key"};
+    int worst = -1;
+    for (int k = 0; k < IJ_KINDS; k++)
+        if (h[k] != ~0ull && (worst < 0 || h[k] < h[worst])) worst = k;
+    if (worst >= 0) {
+        c->err = "wcg_import_json: line " + std::to_string(h[worst]) + ": " + kind[worst];
+        return WCG_EINVAL;
+    }
+    const u64 L = h[4], total = h[5];
+    // measurement (tools/import_json_bench.py): WCG_IMPORT_JSON_STOP = 1 returns after the checking
+    // pass, 2 after the write pass: nothing is aggregated, the context stays as it was.  Read on every
+    // call, like WCG_INDEX_STAGE.
+    u64 stop = 0;
+    (void)cap_env("WCG_IMPORT_JSON_STOP", &stop);
+    if (nlines) *nlines = L;
+    if (stop == 1) return WCG_OK;
+    if (mode == IJ_MAP) {
+        // every line sheds its 22 bytes of framing: the scanned total is n - 22 L
+        if (total != n - IJ_MAP_FIXED * L) { c->err = "wcg_import_json: the key text does not match the file"; return WCG_EHIP; }
+        if (wcg_map_size_check(total) != WCG_OK) { c->err = "wcg_import_json: more keys than one map call takes"; return WCG_EINVAL; }
+        RC(ensure(c, &c->ij_keys, &c->ij_keys_cap, total + 64));
+        k_ij_keys<<<(unsigned)nt, IJ_NT, 0, c->stream>>>(text, n, lines, start, osz, c->ij_keys);
+        HIPCHK(c, hipGetLastError());
+        if (stop == 2) { HIPCHK(c, hipStreamSynchronize(c->stream)); return WCG_OK; }
+        RC(wcg_map_device(c, c->ij_keys, total));
+    } else {
+        RC(ensure(c, &c->ij_units, &c->ij_units_cap, total + 1));
+        k_ij_units<<<(unsigned)nt, IJ_NT, 0, c->stream>>>(text, n, lines, start, osz, c->ij_units);
+        HIPCHK(c, hipGetLastError());
+        if (stop == 2) { HIPCHK(c, hipStreamSynchronize(c->stream)); return WCG_OK; }
+        RC(wcg_import(c, c->ij_units, total));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return WCG_OK;
+}
+
+int wcg_import_json_device(wcg_ctx* c, const void* dev_bytes, uint64_t n, int mode, uint64_t* nlines) {
+    if (!c) return WCG_EINVAL;
+    if (mode != WCG_JSON_MAP && mode != WCG_JSON_RES) { c->err = "wcg_import_json_device: mode"; return WCG_EINVAL; }
+    if (nlines) *nlines = 0;
+    if (n == 0) return WCG_OK;
+    if (!dev_bytes) return WCG_EINVAL;
+    int rc = set_dev(c);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // the last byte, before anything is launched
+    uint8_t last = 0;
+    HIPCHK(c, hipMemcpy(&last, static_cast<const uint8_t*>(dev_bytes) + n - 1, 1, hipMemcpyDeviceToHost));
+    if (last != '\n') { c->err = "wcg_import_json_device: newline (the file does not end with one)"; return WCG_EINVAL; }
+    return import_json(c, static_cast<const uint8_t*>(dev_bytes), n, mode, nlines);
+}
+
+int wcg_import_json(wcg_ctx* c, const uint8_t* host_bytes, uint64_t n, int mode, uint64_t* nlines) {
+    if (!c) return WCG_EINVAL;
+    if (mode != WCG_JSON_MAP && mode != WCG_JSON_RES) { c->err = "wcg_import_json: mode"; return WCG_EINVAL; }
+    if (nlines) *nlines = 0;
+    if (n == 0) return WCG_OK;
+    if (!host_bytes) return WCG_EINVAL;
+    if (host_bytes[n - 1] != '\n') { c->err = "wcg_import_json: newline (the file does not end with one)"; return WCG_EINVAL; }
+    int rc = set_dev(c);
+    if (rc) return rc;
+    // through the ingest's pinned staging buffers, alternating, as wcg_load_merged
+    RC(ingest_init(c));
+    RC(ensure(c, &c->ij_in, &c->ij_in_cap, n + 64));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int slot = 0;
+    bool used[INGEST_SLOTS] = {};
+    for (u64 off = 0; off < n; off += c->chunk, slot = (slot + 1) % INGEST_SLOTS) {
+        const u64 len = std::min<u64>(c->chunk, n - off);
+        if (used[slot]) HIPCHK(c, hipEventSynchronize(c->ev_copied[slot]));
+        memcpy(c->hb[slot], host_bytes + off, len);
+        HIPCHK(c, hipMemcpyAsync(c->ij_in + off, c->hb[slot], len, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_copied[slot], c->stream));
+        used[slot] = true;
+    }
+    return import_json(c, c->ij_in, n, mode, nlines);
 }
 
 int wcg_map_json(wcg_ctx* c, const uint8_t* host_bytes, uint64_t n, uint32_t nreduce, uint8_t* host_out, uint64_t cap,

@@ -6,4 +6,5 @@ Python host side (tests, bench, multi-GPU orchestration) over the C ABI of libwc
 from ._lib import (Engine, WcgError, ihash, load, version, EXPORTED, RECORD_BYTES,  # noqa: F401
                    exchange_plan, gather_plan, exchange_local, gather_merge_local,
                    top_of_merged, top_merge, TOP_MAX,
-                   lookup_in_merged, range_of_merged, prefix_succ, check_merged, MERGED_KINDS)
+                   lookup_in_merged, range_of_merged, prefix_succ, check_merged, MERGED_KINDS,
+                   JSON_MAP, JSON_RES)

@@ -29,10 +29,11 @@ EXPORTED = [
     "wcg_gather_plan", "wcg_exchange_local", "wcg_gather_merge_local", "wcg_reduce_path",
     "wcg_reduce_async", "wcg_reduce_wait", "wcg_ingest_stats", "wcg_top", "wcg_map_size_check",
     "wcg_lookup", "wcg_lookup_device", "wcg_range", "wcg_index_merged", "wcg_load_merged",
-    "wcg_load_merged_device", "wcg_seed_stats",
+    "wcg_load_merged_device", "wcg_seed_stats", "wcg_import_json", "wcg_import_json_device",
 ]
 COMM_ID_BYTES = 128
 TOP_MAX = 1024                            # WCG_TOP_MAX
+JSON_MAP, JSON_RES = 0, 1                 # WCG_JSON_MAP / WCG_JSON_RES: wcg_import_json's modes
 
 
 class WcgError(RuntimeError):
@@ -100,6 +101,8 @@ def load() -> ctypes.CDLL:
         "wcg_index_merged": (I, [P, PU64]),
         "wcg_load_merged": (I, [P, ctypes.c_char_p, U64, PU64]),
         "wcg_load_merged_device": (I, [P, P, U64, PU64]),
+        "wcg_import_json": (I, [P, ctypes.c_char_p, U64, I, PU64]),
+        "wcg_import_json_device": (I, [P, P, U64, I, PU64]),
         "wcg_seed_stats": (I, [P, PU64]),
     }
     for name, (res, args) in sig.items():
@@ -386,6 +389,21 @@ class Engine:
         """wcg_load_merged_device: the same for n bytes in device memory (synchronous)."""
         nl = ctypes.c_uint64()
         self._chk(self._lib.wcg_load_merged_device(self._ctx, ctypes.c_void_p(dev_ptr), n, ctypes.byref(nl)))
+        return nl.value
+
+    def import_json(self, data: bytes, mode: int) -> int:
+        """wcg_import_json: one of the reference's JSON files (mode JSON_MAP: DoMap's per-occurrence
+        intermediates; JSON_RES: a DoReduce -res file) decoded on the GPU and added to the tables, as
+        map_host / import_host add; returns its lines.  A file that breaks a rule raises
+        WcgError(WCG_EINVAL) naming line and rule, and leaves the engine as it was."""
+        nl = ctypes.c_uint64()
+        self._chk(self._lib.wcg_import_json(self._ctx, data if data else None, len(data), mode, ctypes.byref(nl)))
+        return nl.value
+
+    def import_json_device(self, dev_ptr: int, n: int, mode: int) -> int:
+        """wcg_import_json_device: the same for n bytes in device memory (synchronous)."""
+        nl = ctypes.c_uint64()
+        self._chk(self._lib.wcg_import_json_device(self._ctx, ctypes.c_void_p(dev_ptr), n, mode, ctypes.byref(nl)))
         return nl.value
 
     # -- the shuffle and the final Merge over RCCL, inside the library

@@ -12,7 +12,8 @@ Reference pieces mirrored here:
   * the registration server and Run (mapreduce.go:84-133, 358-380);
   * the worker (worker.go:22-92): Register, then serve at most nRPC connections (failure
     injection), DoJob and Shutdown;
-  * Merge (mapreduce.go:284-321) on the host, from the -res-<r> JSON files.
+  * Merge (mapreduce.go:284-321) on the host, from the -res-<r> JSON files (merge), or on the GPU
+    (merge_gpu: the same files decoded by wcg_import_json).
 
 Where the GPU changes the data plane:
   * DoMap runs the split through one wcg engine (tokenize + aggregate on the GPU). It writes its
@@ -160,8 +161,29 @@ def merge(workdir: str, fname: str, nreduce: int) -> bytes:
     return out
 
 
+def merge_gpu(engine, workdir: str, fname: str, nreduce: int) -> bytes:
+    """Merge (mapreduce.go:284-321) on the GPU: every -res-<r> file decoded by the engine
+    (wcg_import_json, RES mode), then one reduce; writes mrtmp.<f> and returns its bytes.  The
+    files of one job hold disjoint keys, so the result is merge()'s; a key in several files would
+    add here where Merge's map keeps the last.  A malformed file raises (merge() reads a file up
+    to its first bad line)."""
+    engine.reset()
+    for r in range(nreduce):
+        print(f"Merge: read {merge_name(fname, r)}", flush=True)
+        with open(os.path.join(workdir, merge_name(fname, r)), "rb") as f:
+            data = f.read()
+        if data:
+            engine.import_json(data, JSON_RES)
+    engine.reduce()
+    out = engine.result()
+    _atomic_write(os.path.join(workdir, "mrtmp." + fname), out)
+    return out
+
+
 # ---------------------------------------------------------------- GPU DoMap / DoReduce
+EINVAL = 1                             # WCG_EINVAL (include/wcg.h): here, a JSON file the GPU refuses
 EFULL = 4                              # WCG_EFULL (include/wcg.h): aggregation table full
+JSON_MAP, JSON_RES = 0, 1              # WCG_JSON_MAP / WCG_JSON_RES
 
 # Quirk P2 (SURVEY 8(a) row 5): DoMap reads its split with ONE file.Read of the split's size
 # (mapreduce.go:205-207), and Go's os.File.Read on Linux moves at most 1 GiB per call
@@ -241,11 +263,22 @@ def do_reduce(engine, job: int, workdir: str, fname: str, nmap: int) -> None:
     # CPU DoMap, or a GPU worker with json_intermediates) - workers of one job may differ.  A record
     # unit never starts with '{' (its first byte is a key byte or zero padding; '{' is no letter).
     is_json = [f[:1] == b"{" for f in files]
+    # an engine that reads the JSON itself (wcg_import_json) takes the file as it is; one without
+    # the call (the CPU stand-ins), or a file the GPU refuses (it accepts only files whose every
+    # line is well-formed, and changes nothing otherwise), keeps the host decode below
+    gpu_json = getattr(engine, "import_json", None)
 
     def run():
         engine.reset()
         for data, js in zip(files, is_json):
             if js:
+                if gpu_json is not None:
+                    try:
+                        gpu_json(data, JSON_MAP)
+                        continue
+                    except Exception as e:
+                        if getattr(e, "status", None) != EINVAL:
+                            raise
                 # decode on the host as DoReduce's json.Decoder does (mapreduce.go:249-261), one
                 # key per line, and count the keys on the GPU
                 keys = _json_keys(data)
