@@ -199,6 +199,44 @@ WCG_API int wcg_lookup_device(wcg_ctx *ctx, const void *dev_keys, const void *de
 WCG_API int wcg_range(wcg_ctx *ctx, const uint8_t *lo, uint64_t lo_len, const uint8_t *hi, uint64_t hi_len,
                       uint8_t *host_out, uint64_t cap, uint64_t *nlines, uint64_t *nbytes);
 
+/* The merged file in count order: its lines as `LC_ALL=C sort -n -k2 <merged file>` prints them
+ * (test-wc.sh:2-3 without the tail) - ascending by count (compared as unsigned 64-bit), lines of
+ * equal count ascending by bytewise key, a prefix before its extensions.  With K the keys of the
+ * result (what wcg_reduce / wcg_index_merged report), rank 0 is the first line of that output and
+ * rank K-1 the most frequent word.  The order is sorted on the device from the sorted records (a
+ * radix sort of (count, record index): no key byte is compared), on the first of these calls after
+ * a result and kept until the next job; wcg_reduce itself launches what it always did.
+ *   wcg_by_count: the lines at ranks [first, min(first + n, K)) to host_out.  first + n saturates
+ * (n = UINT64_MAX: to the end); first >= K or n == 0: no lines (WCG_OK).  *nlines / *nbytes are
+ * always set; host_out == NULL queries them only (the window's lines stay cached on the device
+ * until the next job, so a second call that selects the same lines is a copy); cap < *nbytes:
+ * WCG_EINVAL.  For every n <= WCG_TOP_MAX, wcg_by_count(K - min(n, K), n) gives wcg_top(n)'s bytes.
+ *   wcg_by_count_device: the same lines left in a library-owned device buffer (*dev_ptr; NULL when
+ * there are none).  It is the window cache: valid until the next wcg_by_count* call with another
+ * window or the next job, freed by wcg_close; wcg_free does not take it.
+ *   wcg_count_rank: ranks[i] = the number of keys whose count is below counts[i] (0 .. K), a binary
+ * search per count on the device.  The keys with a count >= c are the ranks [rank(c), K), those
+ * with exactly c the ranks [rank(c), rank(c + 1)).  nq == 0 is WCG_OK and touches nothing; a NULL
+ * pointer with nq > 0: WCG_EINVAL.
+ * State rules as wcg_lookup's (after wcg_index_merged / wcg_load_merged* the calls work as after
+ * wcg_reduce); the result calls, wcg_partition*, wcg_export*, wcg_top, wcg_lookup*, wcg_range,
+ * wcg_stats and wcg_timings in between do not disturb the order.  A device allocation that fails
+ * is WCG_ENOMEM, and the result and its other queries stay as they were.  The order names a record
+ * by a 32-bit index: a result of 2^32 sorted records or more is WCG_EINVAL, checked before
+ * anything is launched. */
+WCG_API int wcg_by_count(wcg_ctx *ctx, uint64_t first, uint64_t n, uint8_t *host_out, uint64_t cap,
+                         uint64_t *nlines, uint64_t *nbytes);
+WCG_API int wcg_by_count_device(wcg_ctx *ctx, uint64_t first, uint64_t n, const void **dev_ptr,
+                                uint64_t *nlines, uint64_t *nbytes);
+WCG_API int wcg_count_rank(wcg_ctx *ctx, const uint64_t *counts, uint64_t nq, uint64_t *ranks);
+
+/* Diagnostics: the last build of the count order.  out[0] = the context holds an order, out[1] =
+ * the digit passes it ran (bit d: the pass over byte d of the counts; a byte in which all counts
+ * agree is skipped), and, when wcg_enable_timing was on during the build, device milliseconds:
+ * out[2] the pass that reads the records, out[3 + d] the pass of digit d (0: skipped).
+ * n = number of doubles the caller provides (<= 11). */
+WCG_API int wcg_by_count_stats(wcg_ctx *ctx, double *out, int n);
+
 /* DoMap's reference-exact intermediate files (mapreduce.go:214-230) for one split: for every
  * token, in input order, the line {"Key":"tok","Value":"1"}\n in file ihash(tok) % nreduce - the
  * bytes the reference's json.Encoder writes to mrtmp.<f>-<m>-<r>, so an unmodified CPU DoReduce

@@ -31,6 +31,7 @@
 #include "wcg_reduce.h"
 #include "wcg_top.h"
 #include "wcg_query.h"
+#include "wcg_bycount.h"
 #include "wcg_index.h"
 #include "wcg_import_json.h"
 #include "wcg_fused.h"
@@ -118,6 +119,28 @@ struct wcg_ctx {
     bool range_ok = false;
     u64 range_a = 0, range_b = 0, range_lines = 0, range_bytes = 0;
     uint8_t* d_range = nullptr; u64 range_cap = 0;
+    // the count order (wcg_by_count / wcg_count_rank, wcg_bycount.h): the items (count, index) of
+    // the sorted records, sorted; valid while bc_ok (built on the first call that needs it, reset
+    // wherever top_n is).  bc_key / bc_idx[bc_cur] hold it, the other pair is the passes' ping-pong;
+    // its first bc_z items are the records of count 0.  The window of ranks [bcw_a, bcw_b) is
+    // cached in d_bc while bcw_ok.
+    bool bc_ok = false;
+    int bc_cur = 0;
+    u64 bc_z = 0;
+    u64* bc_key[2] = {}; u64 bc_key_cap[2] = {};
+    u32* bc_idx[2] = {}; u64 bc_idx_cap[2] = {};
+    u64* bc_hist = nullptr; u64 bc_hist_cap = 0;      // k_bc_items' histograms and zero count
+    u32* bc_thist = nullptr; u64 bc_thist_cap = 0;    // a pass's per-workgroup histogram
+    std::vector<u64> bc_hhist;                        // the host copy of bc_hist
+    u32 bc_passes = 0;                                // bit d: the last build ran digit d's pass
+    std::vector<hipEvent_t> bc_ev;                    // timing (wcg_enable_timing): around the build's passes
+    double bc_ms[1 + 8] = {};
+    bool bcw_ok = false;
+    u64 bcw_a = 0, bcw_b = 0, bcw_lines = 0, bcw_bytes = 0;
+    Rec* bc_rec = nullptr; u64 bc_rec_cap = 0;        // the window's records
+    uint8_t* d_bc = nullptr; u64 bc_cap = 0;          // their lines
+    u64* bc_q = nullptr; u64 bc_q_cap = 0;            // wcg_count_rank's staging: counts, ranks
+    u64* bc_r = nullptr; u64 bc_r_cap = 0;
     // c->sorted[0, sorted_n) still holds the last wcg_reduce's records (wcg_top reads them): set by
     // the reduce; the record buffers' reallocation (a later compaction that needs more) ends it
     bool sorted_live = false;
@@ -1261,7 +1284,10 @@ int wcg_close(wcg_ctx* c) {
                     c->ij_in, c->ij_tiles, c->ij_keys, c->ij_units,
                     c->d_xrow, c->xrecv, c->grecv, c->glist, c->llist, c->fr_buf, c->flist,
                     c->top_cand, c->top_rec, c->d_top, c->q_keys, c->q_off, c->q_cnt, c->rs_part, c->d_range,
+                    c->bc_key[0], c->bc_key[1], c->bc_idx[0], c->bc_idx[1], c->bc_hist, c->bc_thist, c->bc_rec, c->d_bc,
+                    c->bc_q, c->bc_r,
                     c->seed, c->d_clk, c->d_fclk, c->d_stamps};
+    for (auto e : c->bc_ev) (void)hipEventDestroy(e);
     if (c->comm) (void)ncclCommDestroy(c->comm);
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (c->h_x) (void)hipHostFree(c->h_x);
@@ -1396,7 +1422,7 @@ int reset_tables(wcg_ctx* c) {
     c->counts_clean = true;
     c->compacted = c->reduced = c->merged = false;
     c->exp_ready = false;
-    c->part_R = 0; c->top_n = 0; c->range_ok = false;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false; c->bc_ok = false; c->bcw_ok = false;
     c->nrec = 0;
     c->out_len = 0;
     c->two_pass_used = false;
@@ -1804,7 +1830,7 @@ int wcg_map_device(wcg_ctx* c, const void* dev_bytes, uint64_t n) {
     c->map_launches_since_reset++;
     c->compacted = c->reduced = c->merged = false;
     c->exp_ready = false;
-    c->part_R = 0; c->top_n = 0; c->range_ok = false;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false; c->bc_ok = false; c->bcw_ok = false;
     return WCG_OK;
 }
 
@@ -1894,7 +1920,7 @@ int wcg_reduce(wcg_ctx* c, uint64_t* nkeys, uint64_t* nbytes) {
         }
         c->reduced = true;
         c->merged = false;
-        c->part_R = 0; c->top_n = 0; c->range_ok = false;
+        c->part_R = 0; c->top_n = 0; c->range_ok = false; c->bc_ok = false; c->bcw_ok = false;
         if (nkeys) *nkeys = c->nkeys;
         if (nbytes) *nbytes = c->out_len;
         return WCG_OK;
@@ -1945,7 +1971,7 @@ int wcg_reduce(wcg_ctx* c, uint64_t* nkeys, uint64_t* nbytes) {
     c->sorted_live = true;
     c->sorted_n = c->nrec;
     c->reduced = true;
-    c->part_R = 0; c->top_n = 0; c->range_ok = false;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false; c->bc_ok = false; c->bcw_ok = false;
     if (nkeys) *nkeys = c->nkeys;
     if (nbytes) *nbytes = c->out_len;
     return WCG_OK;
@@ -1969,7 +1995,7 @@ int wcg_reduce_async(wcg_ctx* c) {
     c->pending = true;
     c->reduced = true;
     c->merged = false;
-    c->part_R = 0; c->top_n = 0; c->range_ok = false;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false; c->bc_ok = false; c->bcw_ok = false;
     return WCG_OK;
 }
 
@@ -2285,6 +2311,184 @@ int wcg_range(wcg_ctx* c, const uint8_t* lo, uint64_t lo_len, const uint8_t* hi,
     return WCG_OK;
 }
 
+// ensure() for the count order's buffers: a failed allocation is WCG_ENOMEM (and nothing else of
+// the context has changed: these buffers are the count order's own)
+#define BC_ENSURE(c, p, cap, need) bc_nomem(c, ensure(c, p, cap, need), *(p))
+static int bc_nomem(wcg_ctx* c, int rc, const void* buf) {
+    if (rc == WCG_EHIP && !buf) {
+        (void)hipGetLastError();
+        c->err = "wcg_by_count: device allocation failed (" + c->err + ")";
+        return WCG_ENOMEM;
+    }
+    return rc;
+}
+
+// the count order of c->sorted[0, sorted_n) in c->bc_key / bc_idx[bc_cur] (kept until the next job)
+static int bc_build(wcg_ctx* c) {
+    if (c->bc_ok) return WCG_OK;
+    const u64 n = c->sorted_n;
+    // the items carry their record's index in 32 bits
+    if (n >> 32) { c->err = "wcg_by_count: 2^32 sorted records or more"; return WCG_EINVAL; }
+    c->bcw_ok = false;
+    c->bc_z = 0; c->bc_cur = 0; c->bc_passes = 0;
+    for (double& m : c->bc_ms) m = 0;
+    if (n == 0) { c->bc_ok = true; return WCG_OK; }
+    for (int s = 0; s < 2; s++) {
+        RC(BC_ENSURE(c, &c->bc_key[s], &c->bc_key_cap[s], n));
+        RC(BC_ENSURE(c, &c->bc_idx[s], &c->bc_idx_cap[s], n));
+    }
+    RC(BC_ENSURE(c, &c->bc_hist, &c->bc_hist_cap, (u64)BC_HIST));
+    RC(BC_ENSURE(c, &c->bc_thist, &c->bc_thist_cap, (u64)BC_BINS * BC_MAXG));
+    c->bc_hhist.resize(BC_HIST);
+    const bool timed = c->timing;
+    if (timed)
+        while (c->bc_ev.size() < 2 + 2 * BC_DIGITS) {
+            hipEvent_t e;
+            HIPCHK(c, hipEventCreate(&e));
+            c->bc_ev.push_back(e);
+        }
+    // Workgroups take tiles of BC_TILE items: k_bc_items strides over them, a pass gives each
+    // workgroup tpg consecutive ones (the scatter is stable because a workgroup's items are
+    // consecutive).  tests: WCG_BYCOUNT_GRID may only lower the grid (a few thousand keys then give
+    // a workgroup many tiles); read on every call like WCG_TOP_GRID
+    const u64 ntiles = cdiv(n, BC_TILE);
+    u64 grid = std::min<u64>(ntiles, BC_MAXG), v;
+    if (cap_env("WCG_BYCOUNT_GRID", &v)) grid = std::max<u64>(1, std::min(grid, v));
+    const u64 tpg = cdiv(ntiles, grid);
+    const u64 G = cdiv(ntiles, tpg);                 // <= grid: no workgroup without a tile
+    HIPCHK(c, hipMemsetAsync(c->bc_hist, 0, BC_HIST * sizeof(u64), c->stream));
+    if (timed) HIPCHK(c, hipEventRecord(c->bc_ev[0], c->stream));
+    k_bc_items<<<(unsigned)grid, BC_NT, 0, c->stream>>>(c->sorted, n, c->bc_key[0], c->bc_idx[0], c->bc_hist);
+    HIPCHK(c, hipGetLastError());
+    if (timed) HIPCHK(c, hipEventRecord(c->bc_ev[1], c->stream));
+    // the one read-back: the schedule is the digits in which the counts differ
+    HIPCHK(c, hipMemcpyAsync(c->bc_hhist.data(), c->bc_hist, BC_HIST * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    u32 passes = 0;
+    for (int d = 0; d < BC_DIGITS; d++) {
+        int used = 0;
+        for (int b = 0; b < BC_BINS; b++) used += c->bc_hhist[d * BC_BINS + b] != 0;
+        if (used > 1) passes |= 1u << d;
+    }
+    int cur = 0;
+    for (int d = 0; d < BC_DIGITS; d++) {
+        if (!(passes >> d & 1)) continue;
+        if (timed) HIPCHK(c, hipEventRecord(c->bc_ev[2 + 2 * d], c->stream));
+        k_bc_count<<<(unsigned)G, BC_NT, 0, c->stream>>>(c->bc_key[cur], n, 8u * d, (u32)tpg, c->bc_thist);
+        k_bc_scan<<<1, BC_SCAN_NT, 0, c->stream>>>(c->bc_thist, (u32)(BC_BINS * G));
+        k_bc_scatter<<<(unsigned)G, BC_NT, 0, c->stream>>>(c->bc_key[cur], c->bc_idx[cur], n, 8u * d, (u32)tpg, c->bc_thist,
+                                                           c->bc_key[cur ^ 1], c->bc_idx[cur ^ 1]);
+        HIPCHK(c, hipGetLastError());
+        if (timed) HIPCHK(c, hipEventRecord(c->bc_ev[3 + 2 * d], c->stream));
+        cur ^= 1;
+    }
+    if (timed) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->bc_ev[0], c->bc_ev[1]));
+        c->bc_ms[0] = ms;
+        for (int d = 0; d < BC_DIGITS; d++)
+            if (passes >> d & 1) {
+                HIPCHK(c, hipEventElapsedTime(&ms, c->bc_ev[2 + 2 * d], c->bc_ev[3 + 2 * d]));
+                c->bc_ms[1 + d] = ms;
+            }
+    }
+    c->bc_cur = cur;
+    c->bc_passes = passes;
+    c->bc_z = c->bc_hhist[BC_HIST - 1];
+    c->bc_ok = true;
+    return WCG_OK;
+}
+
+// the lines at ranks [first, min(first + n, K)) of the count order in c->d_bc (cached until the next job)
+static int bc_window(wcg_ctx* c, u64 first, u64 n) {
+    RC(bc_build(c));
+    const u64 K = c->sorted_n - c->bc_z;
+    u64 a = std::min(first, K), b = n > K - a ? K : a + n;      // first + n saturates
+    if (a == b) a = b = 0;                                      // no lines: one cache entry
+    if (c->bcw_ok && c->bcw_a == a && c->bcw_b == b) return WCG_OK;
+    c->bcw_ok = false;
+    u64 lines = 0, bytes = 0;
+    if (a < b) {
+        const u64 m = b - a;
+        RC(BC_ENSURE(c, &c->bc_rec, &c->bc_rec_cap, m));
+        RC(BC_ENSURE(c, &c->rs_part, &c->rs_part_cap, 2 * (u64)RS_MAXG + 2));
+        const u64 grid = std::min<u64>(cdiv(m, RS_NT), RS_MAXG);
+        u64* const tot = c->rs_part + 2 * RS_MAXG;
+        k_bc_gather<<<(unsigned)std::min<u64>(cdiv(m, BC_NT), 2048), BC_NT, 0, c->stream>>>(
+            c->sorted, c->sorted_n, c->bc_idx[c->bc_cur], c->bc_z + a, m, c->bc_rec);
+        k_range_size<<<(unsigned)grid, RS_NT, 0, c->stream>>>(c->bc_rec, 0, m, c->rs_part);
+        k_range_total<<<1, RS_NT, 0, c->stream>>>(c->rs_part, (u32)grid, tot);
+        HIPCHK(c, hipGetLastError());
+        // {lines, bytes}: the formatter's buffer is sized exactly, as wcg_range's is
+        u64* const h = c->h_scalar + 26;
+        HIPCHK(c, hipMemcpyAsync(h, tot, 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        lines = h[0]; bytes = h[1];
+        if (lines != m) { c->err = "wcg_by_count: a record without a count inside the order"; return WCG_EHIP; }
+        u64 got = 0;
+        int rc = format(c, c->bc_rec, m, sorted_arena(c), FMT_MERGED, 1, 0, bytes, &c->d_bc, &c->bc_cap, &got);
+        if (rc == WCG_EHIP && !c->d_bc) { (void)hipGetLastError(); rc = WCG_ENOMEM; }
+        RC(rc);
+        if (got != bytes) { c->err = "wcg_by_count: formatted size mismatch"; return WCG_EHIP; }
+    }
+    c->bcw_a = a; c->bcw_b = b;
+    c->bcw_lines = lines; c->bcw_bytes = bytes;
+    c->bcw_ok = true;
+    return WCG_OK;
+}
+
+int wcg_by_count_device(wcg_ctx* c, uint64_t first, uint64_t n, const void** dev_ptr, uint64_t* nlines, uint64_t* nbytes) {
+    if (!c) return WCG_EINVAL;
+    if (nlines) *nlines = 0;
+    if (nbytes) *nbytes = 0;
+    if (dev_ptr) *dev_ptr = nullptr;
+    RC(query_state(c, "wcg_by_count"));
+    RC(bc_window(c, first, n));
+    if (nlines) *nlines = c->bcw_lines;
+    if (nbytes) *nbytes = c->bcw_bytes;
+    if (dev_ptr) *dev_ptr = c->bcw_bytes ? c->d_bc : nullptr;
+    return WCG_OK;
+}
+
+int wcg_by_count(wcg_ctx* c, uint64_t first, uint64_t n, uint8_t* host_out, uint64_t cap, uint64_t* nlines,
+                 uint64_t* nbytes) {
+    RC(wcg_by_count_device(c, first, n, nullptr, nlines, nbytes));
+    if (host_out) {
+        if (cap < c->bcw_bytes) { c->err = "wcg_by_count: buffer too small"; return WCG_EINVAL; }
+        if (c->bcw_bytes) {
+            HIPCHK(c, hipMemcpyAsync(host_out, c->d_bc, c->bcw_bytes, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    return WCG_OK;
+}
+
+int wcg_count_rank(wcg_ctx* c, const uint64_t* counts, uint64_t nq, uint64_t* ranks) {
+    if (!c) return WCG_EINVAL;
+    RC(query_state(c, "wcg_count_rank"));
+    if (nq == 0) return WCG_OK;
+    if (!counts || !ranks) { c->err = "wcg_count_rank: null counts or ranks"; return WCG_EINVAL; }
+    RC(bc_build(c));
+    RC(BC_ENSURE(c, &c->bc_q, &c->bc_q_cap, nq));
+    RC(BC_ENSURE(c, &c->bc_r, &c->bc_r_cap, nq));
+    HIPCHK(c, hipMemcpyAsync(c->bc_q, counts, nq * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    k_bc_rank<<<(unsigned)std::min<u64>(cdiv(nq, BC_NT), 2048), BC_NT, 0, c->stream>>>(
+        c->bc_key[c->bc_cur], c->sorted_n, c->bc_z, c->bc_q, nq, c->bc_r);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(ranks, c->bc_r, nq * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return WCG_OK;
+}
+
+int wcg_by_count_stats(wcg_ctx* c, double* out, int n) {
+    if (!c || !out || n < 0 || n > 11) return WCG_EINVAL;
+    const double v[11] = {(double)c->bc_ok, (double)c->bc_passes, c->bc_ms[0], c->bc_ms[1], c->bc_ms[2], c->bc_ms[3],
+                          c->bc_ms[4], c->bc_ms[5], c->bc_ms[6], c->bc_ms[7], c->bc_ms[8]};
+    for (int i = 0; i < n; i++) out[i] = v[i];
+    return WCG_OK;
+}
+
 int wcg_export_count(wcg_ctx* c, uint32_t nreduce, uint32_t nranks, uint64_t* counts) {
     if (!c || !counts || nreduce == 0 || nranks == 0 || nranks > EX_MAX_RANKS) return WCG_EINVAL;
     RC(resolve(c));
@@ -2352,7 +2556,7 @@ int wcg_import(wcg_ctx* c, const void* dev_records, uint64_t nrecords) {
     c->imported = true;
     c->compacted = c->reduced = c->merged = false;
     c->exp_ready = false;
-    c->part_R = 0; c->top_n = 0; c->range_ok = false;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false; c->bc_ok = false; c->bcw_ok = false;
     return WCG_OK;          // a full table is reported by the next wcg_reduce / wcg_export_count
 }
 
@@ -2370,7 +2574,7 @@ static int merge_runs(wcg_ctx* c, const void* dev_text, const uint64_t* run_byte
     for (u32 r = 0; r < nruns; r++) total += run_bytes[r];
     c->compacted = false;
     c->exp_ready = false;
-    c->part_R = 0; c->top_n = 0; c->range_ok = false;
+    c->part_R = 0; c->top_n = 0; c->range_ok = false; c->bc_ok = false; c->bcw_ok = false;
     c->reduced = false;
     if (total == 0) {
         c->nrec = 0; c->nkeys = 0; c->out_len = 0; c->reduced = true; c->merged = true;
@@ -2487,7 +2691,7 @@ int wcg_index_merged(wcg_ctx* c, uint64_t* nlines) {
     c->sorted_n = L;
     c->sorted_live = true;
     c->indexed = true;
-    c->top_n = 0; c->range_ok = false;
+    c->top_n = 0; c->range_ok = false; c->bc_ok = false; c->bcw_ok = false;
     if (nlines) *nlines = L;
     return WCG_OK;
 }

@@ -7,4 +7,5 @@ from ._lib import (Engine, WcgError, ihash, load, version, EXPORTED, RECORD_BYTE
                    exchange_plan, gather_plan, exchange_local, gather_merge_local,
                    top_of_merged, top_merge, TOP_MAX,
                    lookup_in_merged, range_of_merged, prefix_succ, check_merged, MERGED_KINDS,
-                   JSON_MAP, JSON_RES)
+                   JSON_MAP, JSON_RES,
+                   by_count_of_merged, count_rank_of_merged, by_count_merge)

@@ -30,9 +30,11 @@ EXPORTED = [
     "wcg_reduce_async", "wcg_reduce_wait", "wcg_ingest_stats", "wcg_top", "wcg_map_size_check",
     "wcg_lookup", "wcg_lookup_device", "wcg_range", "wcg_index_merged", "wcg_load_merged",
     "wcg_load_merged_device", "wcg_seed_stats", "wcg_import_json", "wcg_import_json_device",
+    "wcg_by_count", "wcg_by_count_device", "wcg_count_rank", "wcg_by_count_stats",
 ]
 COMM_ID_BYTES = 128
 TOP_MAX = 1024                            # WCG_TOP_MAX
+U64_MAX = (1 << 64) - 1
 JSON_MAP, JSON_RES = 0, 1                 # WCG_JSON_MAP / WCG_JSON_RES: wcg_import_json's modes
 
 
@@ -104,6 +106,10 @@ def load() -> ctypes.CDLL:
         "wcg_import_json": (I, [P, ctypes.c_char_p, U64, I, PU64]),
         "wcg_import_json_device": (I, [P, P, U64, I, PU64]),
         "wcg_seed_stats": (I, [P, PU64]),
+        "wcg_by_count": (I, [P, U64, U64, P, U64, PU64, PU64]),
+        "wcg_by_count_device": (I, [P, U64, U64, ctypes.POINTER(P), PU64, PU64]),
+        "wcg_count_rank": (I, [P, PU64, U64, PU64]),
+        "wcg_by_count_stats": (I, [P, ctypes.POINTER(ctypes.c_double), I]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WCG_LIB") and not hasattr(lib, name):
@@ -340,6 +346,69 @@ class Engine:
     def prefix(self, p: bytes) -> bytes:
         """The merged file's lines whose key starts with p: range(p, prefix_succ(p))."""
         return self.range(p, prefix_succ(p))
+
+    @staticmethod
+    def _window(first: int, n: Optional[int]) -> Tuple[int, int]:
+        n = U64_MAX if n is None else n
+        if not (0 <= first <= U64_MAX and 0 <= n <= U64_MAX):
+            raise WcgError(WCG_EINVAL, "by_count: first or n out of range")
+        return first, n
+
+    def by_count_size(self, first: int = 0, n: Optional[int] = None) -> Tuple[int, int]:
+        """wcg_by_count with host_out == NULL: (lines, bytes) of by_count(first, n); the lines stay
+        on the device."""
+        first, n = self._window(first, n)
+        nl, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._lib.wcg_by_count(self._ctx, first, n, None, 0, ctypes.byref(nl), ctypes.byref(nb)))
+        return nl.value, nb.value
+
+    def by_count(self, first: int = 0, n: Optional[int] = None) -> bytes:
+        """The lines at ranks [first, first + n) of the merged file in count order (n = None: to the
+        end), sorted and formatted on the device: what by_count_of_merged(result(), first, n)
+        computes, the bytes of `LC_ALL=C sort -n -k2 <merged file>` from line `first` on."""
+        first, n = self._window(first, n)
+        _, nb = self.by_count_size(first, n)
+        buf = ctypes.create_string_buffer(max(nb, 1))
+        nl2, nb2 = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._lib.wcg_by_count(self._ctx, first, n, buf, nb, ctypes.byref(nl2), ctypes.byref(nb2)))
+        return buf.raw[:nb2.value]
+
+    def by_count_device(self, first: int = 0, n: Optional[int] = None) -> Tuple[int, int, int]:
+        """wcg_by_count_device: (device pointer, lines, bytes) of the same lines, left in the
+        engine's window buffer (valid until the next by_count* call with another window, or the
+        next job)."""
+        first, n = self._window(first, n)
+        p, nl, nb = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._lib.wcg_by_count_device(self._ctx, first, n, ctypes.byref(p), ctypes.byref(nl), ctypes.byref(nb)))
+        return p.value or 0, nl.value, nb.value
+
+    def count_rank(self, counts: Sequence[int]) -> List[int]:
+        """For every count c asked, the number of keys of the last reduce whose count is below c
+        (wcg_count_rank: binary searches over the count order on the device).  The keys with a
+        count >= c are the ranks [rank(c), keys) of by_count."""
+        nq = len(counts)
+        if nq == 0:
+            self._chk(self._lib.wcg_count_rank(self._ctx, None, 0, None))
+            return []
+        if not all(0 <= int(c) <= U64_MAX for c in counts):
+            raise WcgError(WCG_EINVAL, "count_rank: a count outside 0 .. 2^64-1")
+        q = (ctypes.c_uint64 * nq)(*[int(c) for c in counts])
+        r = (ctypes.c_uint64 * nq)()
+        self._chk(self._lib.wcg_count_rank(self._ctx, q, nq, r))
+        return list(r)
+
+    def at_least(self, c: int) -> bytes:
+        """The lines whose count is at least c, in count order: one rank, then one window."""
+        return self.by_count(self.count_rank([c])[0], None)
+
+    def by_count_stats(self) -> dict:
+        """The last build of the count order (wcg_by_count_stats): whether the engine holds one, the
+        digit passes it ran, and (with enable_timing on during the build) their device ms."""
+        v = (ctypes.c_double * 11)()
+        self._chk(self._lib.wcg_by_count_stats(self._ctx, v, 11))
+        mask = int(v[1])
+        return {"built": bool(v[0]), "digits": [d for d in range(8) if mask >> d & 1], "items_ms": v[2],
+                "pass_ms": {d: v[3 + d] for d in range(8) if mask >> d & 1}}
 
     def export(self, nreduce: int, nranks: int) -> Tuple[int, List[int]]:
         """Bucket the local aggregate by owner rank; returns (device ptr, units per rank)."""
@@ -600,6 +669,33 @@ def top_merge(parts: List[bytes], n: int) -> bytes:
     items = [it for p in parts for it in _count_lines(p)]
     items.sort()
     return _lines_of(items[-n:])
+
+
+def by_count_of_merged(merged: bytes, first: int = 0, n: Optional[int] = None) -> bytes:
+    """What Engine.by_count(first, n) computes, stated on the host: the merged file's lines after a
+    stable sort by count (the bytes of `LC_ALL=C sort -n -k2 <merged file>`: ascending counts, lines
+    of equal count in the file's key order), from line `first` on, n lines at most (None: all)."""
+    items = _count_lines(merged)
+    items.sort(key=lambda it: it[0])                # stable: ties keep the file's key order
+    first = max(0, first)
+    return _lines_of(items[first:] if n is None else items[first:first + max(0, n)])
+
+
+def count_rank_of_merged(merged: bytes, counts: Sequence[int]) -> List[int]:
+    """What Engine.count_rank(counts) computes, stated on the host: for every count asked, the
+    number of the merged file's lines whose count is below it."""
+    import bisect
+    have = sorted(c for c, _ in _count_lines(merged))
+    return [bisect.bisect_left(have, int(c)) for c in counts]
+
+
+def by_count_merge(parts: List[bytes]) -> bytes:
+    """The whole job's count order from the count orders of ranks that own disjoint keys
+    (Engine.by_count() on every rank after exchange + reduce), combined on the host.  The parts are
+    not in one key order, so the order is (count, key bytes) outright, as in top_merge."""
+    items = [it for p in parts for it in _count_lines(p)]
+    items.sort()
+    return _lines_of(items)
 
 
 def _key_lines(merged: bytes) -> List[Tuple[bytes, bytes]]:

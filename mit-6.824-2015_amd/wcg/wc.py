@@ -9,6 +9,12 @@
   python -m wcg.wc count <file> <word>...            "<word>: <count>" per argument, in argument
                                                      order, zeros included, looked up on the GPU
   python -m wcg.wc prefix <file> <P>                 the merged file's lines whose key starts with P
+  python -m wcg.wc by-count <file> [FIRST [N]]       the merged file in count order, what `sort -n -k2
+                                                     mrtmp.<file>` prints, from line FIRST (default 0)
+                                                     on, N lines (default: all), sorted on the GPU
+  python -m wcg.wc at-least <file> <C>               its lines whose count is at least C, in that order
+  python -m wcg.wc by-count-merged <mrtmp> [FIRST [N]]   the same two asked of a merged file that
+  python -m wcg.wc at-least-merged <mrtmp> <C>           already exists
   python -m wcg.wc top-merged <mrtmp> <N>            the same three questions asked of a merged file
   python -m wcg.wc count-merged <mrtmp> <word>...    that already exists (mrtmp.<file>, ours or the
   python -m wcg.wc prefix-merged <mrtmp> <P>         CPU reference's): checked, loaded and searched
@@ -168,7 +174,33 @@ def prefix_merged(path: str, p: bytes) -> bytes:
     return _loaded(path, lambda e: e.prefix(p))
 
 
+def by_count(path: str, first: int = 0, n=None) -> bytes:
+    """The merged file of a file in count order (`sort -n -k2`), lines [first, first + n) of it
+    (n = None: to the end), sorted on the GPU (Engine.by_count); writes no mrtmp.* files."""
+    return _reduced(path, lambda e: e.by_count(first, n))
+
+
+def at_least(path: str, c: int) -> bytes:
+    """The merged file's lines of a file whose count is at least c, in count order (Engine.at_least)."""
+    return _reduced(path, lambda e: e.at_least(c))
+
+
+def by_count_merged(path: str, first: int = 0, n=None) -> bytes:
+    """by_count() asked of a merged file."""
+    return _loaded(path, lambda e: e.by_count(first, n))
+
+
+def at_least_merged(path: str, c: int) -> bytes:
+    """at_least() asked of a merged file."""
+    return _loaded(path, lambda e: e.at_least(c))
+
+
 def main(argv) -> int:
+    if 3 <= len(argv) <= 5 and argv[1] in ("by-count", "by-count-merged"):
+        fn = by_count if argv[1] == "by-count" else by_count_merged
+        sys.stdout.buffer.write(fn(argv[2], int(argv[3]) if len(argv) > 3 else 0, int(argv[4]) if len(argv) > 4 else None))
+        sys.stdout.buffer.flush()
+        return 0
     if len(argv) >= 4 and argv[1] == "count-merged":
         words = [os.fsencode(w) for w in argv[3:]]
         out = b"".join(w + b": %d\n" % n for w, n in zip(words, count_merged(argv[2], words)))
@@ -192,6 +224,12 @@ def main(argv) -> int:
             mr.MapReduce(NMAP, NREDUCE, argv[2], argv[3], workdir).wait()
     elif argv[1] == "top":
         sys.stdout.buffer.write(top(argv[2], int(argv[3])))
+        sys.stdout.buffer.flush()
+    elif argv[1] == "at-least":
+        sys.stdout.buffer.write(at_least(argv[2], int(argv[3])))
+        sys.stdout.buffer.flush()
+    elif argv[1] == "at-least-merged":
+        sys.stdout.buffer.write(at_least_merged(argv[2], int(argv[3])))
         sys.stdout.buffer.flush()
     elif argv[1] == "top-merged":
         sys.stdout.buffer.write(top_merged(argv[2], int(argv[3])))
